@@ -1,7 +1,11 @@
 """Benchmark of the hot path: one "step" = one progressive frame of the per-pixel path tracer
 (RayTracing/main_raytracing.cu:162-200 via raytracing_process) over the whole frame.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--dump-outputs DIR] [--full]
+
+A plain run sets up (scene, tile order, lane map, occupancy), warms up, times the K steps, writes the last
+step's frame if --dump-outputs is given, and prints the result line.  --full adds everything else described
+below: the bit-exact checks, frame 0's traversal counts, the roofline with its PMC pass, and the CPU baseline.
 
 N = 1 runs BASELINE.json configs[1] (Stanford bunny scene, 1920x1080, 8 spp, 6 bounces), its 16x16
 tiles launched heaviest first (--plan cost: one untimed probe frame's per-wave clocks order them;
@@ -772,27 +776,28 @@ def run(args):
         torch.cuda.synchronize()
         return 0
 
-    # --- exact traversal counts of one frame (stats kernel variant) on a copy of the RNG state
-    rng_saved = rng.clone()
-    stats = torch.zeros(rt.STAT_COUNT, dtype=torch.int64, device=dev)
-    render(0, bufs[0], bufs[1], stats=stats)
-    torch.cuda.synchronize()
-    rng.copy_(rng_saved)
-    del rng_saved
-    stats0 = stats.cpu().numpy().astype(np.uint64)
-    # --- the production kernel's own work on the same frame and launch shape: its timing variant (RT_TUNE
-    #     bit 8: per-wave phase clocks, small-step iterations and lane-steps, big-leaf tests by twins)
-    prod0 = None
-    if not args.foreign and args.tracer == "fast" and not args.refill:
+    stats0 = prod0 = bytes0 = None
+    if args.full:
+        # --- exact traversal counts of one frame (stats kernel variant) on a copy of the RNG state
         rng_saved = rng.clone()
-        tst = torch.zeros(rt.STAT_COUNT, dtype=torch.int64, device=dev)
-        render(0, bufs[0], bufs[1], stats=tst, tune=args.tune | 256)
+        stats = torch.zeros(rt.STAT_COUNT, dtype=torch.int64, device=dev)
+        render(0, bufs[0], bufs[1], stats=stats)
         torch.cuda.synchronize()
         rng.copy_(rng_saved)
         del rng_saved
-        prod0 = production_counts(dict(zip(rt.STAT_NAMES, tst.cpu().numpy().astype(np.int64).tolist())))
-    gpu = scene.gpu.contents
-    bytes0 = algorithmic_bytes(stats0, gpu.sphere_count, pixels_rank)
+        stats0 = stats.cpu().numpy().astype(np.uint64)
+        # --- the production kernel's own work on the same frame and launch shape: its timing variant (RT_TUNE
+        #     bit 8: per-wave phase clocks, small-step iterations and lane-steps, big-leaf tests by twins)
+        if not args.foreign and args.tracer == "fast" and not args.refill:
+            rng_saved = rng.clone()
+            tst = torch.zeros(rt.STAT_COUNT, dtype=torch.int64, device=dev)
+            render(0, bufs[0], bufs[1], stats=tst, tune=args.tune | 256)
+            torch.cuda.synchronize()
+            rng.copy_(rng_saved)
+            del rng_saved
+            prod0 = production_counts(dict(zip(rt.STAT_NAMES, tst.cpu().numpy().astype(np.int64).tolist())))
+        gpu = scene.gpu.contents
+        bytes0 = algorithmic_bytes(stats0, gpu.sphere_count, pixels_rank)
     if args.foreign and rt.foreign_last_tracer(target) != 1:
         raise RuntimeError("--foreign: the production tracer did not render the frame")
 
@@ -918,25 +923,29 @@ def run(args):
                        if comm is not None else "host clock around the synchronous gather + unshard (rehearsal)",
                        "overlapped_with_next_frame": comm is not None}
 
-    seg_per_launch = segs / args.steps
-    bytes_per_launch = bytes0 * (seg_per_launch / max(1, int(stats0[0])))
     final = frame if sharded else bufs[(n_total - 1) & 1]
     result = None
     if rank == 0:
         img = rt.surface_view(final, W)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, img)
         bad = (~torch.isfinite(img)).any(-1).nonzero()
         finite = bad.shape[0] == 0
-        pmc, err = None, "PMC pass runs at N = 1 only (the rank-0 shard's counters are not the job's)"
-        if world == 1:
-            if args.no_pmc or under_profiler():
-                err = "skipped (--no-pmc or already under a profiler)"
-            else:
-                with tempfile.TemporaryDirectory() as td:
-                    pmc, err = pmc_pass(args, args.pmc_dir or td)
-        roof = roofline(pmc, kern_avg_s, bytes_per_launch, err)
-        roof["frame0_counts"] = {k: int(v) for k, v in zip(rt.STAT_NAMES, stats0) if k and int(v)}
-        if prod0:
-            roof["frame0_production"] = prod0
+        roof = None
+        if args.full:
+            seg_per_launch = segs / args.steps
+            bytes_per_launch = bytes0 * (seg_per_launch / max(1, int(stats0[0])))
+            pmc, err = None, "PMC pass runs at N = 1 only (the rank-0 shard's counters are not the job's)"
+            if world == 1:
+                if args.no_pmc or under_profiler():
+                    err = "skipped (--no-pmc or already under a profiler)"
+                else:
+                    with tempfile.TemporaryDirectory() as td:
+                        pmc, err = pmc_pass(args, args.pmc_dir or td)
+            roof = roofline(pmc, kern_avg_s, bytes_per_launch, err)
+            roof["frame0_counts"] = {k: int(v) for k, v in zip(rt.STAT_NAMES, stats0) if k and int(v)}
+            if prod0:
+                roof["frame0_production"] = prod0
         result = {
             "metric": "Mrays/s + achieved HBM GB/s, Stanford bunny 1920x1080x8spp @1/2/4/8 GPU",
             "value": round(segs_total / elapsed / 1e6, 2),
@@ -954,11 +963,16 @@ def run(args):
                        "bounces": BOUNCES, "parallelism": f"tiles{world}" if sharded else "single",
                        "camera_samples_per_s": round(W * H * SPP * args.steps / elapsed, 1),
                        "segments_per_step": round(segs_total / args.steps, 1), "tracer": args.tracer},
+            "full": args.full,
             "roofline": roof,
             "rank_kernel_ms": [round(x, 3) for x in rank_kernel_ms],
             "setup_s": round(setup_s, 2),
             "image_finite": finite,
         }
+        if roof is None:  # a plain run: the roofline needs runs of its own (--full)
+            del result["roofline"]
+        if args.dump_outputs:
+            result["outputs"] = os.path.abspath(args.dump_outputs)
         if plan_info or sharded:
             result["plan"] = dict(plan_info or {"kind": "round-robin"},
                                   tiles_per_rank=[int(c) for c in counts] if sharded else None)
@@ -977,7 +991,7 @@ def run(args):
                                           "no lane map) on this GPU, final surface compared bit for bit"}
             if fixture is not None:
                 result["check_oracle_fixture"] = fixture
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             auto_rows = {"cfg1": 256, "cfg2": 1080, "cfg3": 64, "cfg4": 540, "cfg5": 1080}[args.config]
             result["cpu_baseline"] = cpu_baseline_child(args.config, args.cpu_rows or auto_rows)
         print(json.dumps(result), flush=True)
@@ -1015,6 +1029,48 @@ def foreign_copy(rt, scene):
             raise RuntimeError(rt.lib().rt_last_error().decode())
         setattr(f, k, p.value)
     return f
+
+
+DUMP_MAX_BYTES = 60 * 10 ** 6  # under 64 MB with the file header, whichever way a megabyte is counted
+
+
+DUMP_PIXEL_BYTES = 16 + 4  # a float4 pixel of frame.npy and its float32 entry of frame_nonfinite.npy
+
+
+def dump_sample(pixels, max_bytes=DUMP_MAX_BYTES):
+    """Which pixels of a `pixels`-pixel float4 frame --dump-outputs writes: None = all of them, else the sorted
+    row-major indices of a fixed sample (seeded by SEED, so two builds write the same pixels) that fits `max_bytes`."""
+    if pixels * DUMP_PIXEL_BYTES <= max_bytes:
+        return None
+    return np.sort(np.random.default_rng(SEED).choice(pixels, max_bytes // DUMP_PIXEL_BYTES, replace=False))
+
+
+def split_nonfinite(a):
+    """A float32 [..., 4] frame as two finite arrays that together hold all of it: the frame with 0 in place of
+    every non-finite component, and per pixel a code of where those were and what -- sum over components c of
+    kind * 4**c, kind 0 = finite, 1 = NaN, 2 = +inf, 3 = -inf (at most 255, exact in float32).  The reference's
+    arithmetic can leave a NaN pixel in a frame (DESIGN.md section 5), which the progressive lerp then keeps;
+    arrays that are compared value by value need it out of band."""
+    a = np.asarray(a, dtype=np.float32)
+    kind = np.where(np.isnan(a), 1, np.where(a == np.inf, 2, np.where(a == -np.inf, 3, 0)))
+    codes = (kind * (4 ** np.arange(a.shape[-1]))).sum(-1).astype(np.float32)
+    return np.where(kind == 0, a, np.float32(0)), codes
+
+
+def dump_outputs(out_dir, img):
+    """--dump-outputs: the last timed step's frame, `img` = the [H, W, 4] float32 view of the surface rt_render
+    filled (N > 1: the frame rank 0 gathered), as out_dir/frame.npy [H, W, 4] and out_dir/frame_nonfinite.npy
+    [H, W] (split_nonfinite: all zero for a finite frame).  The scene, the camera and the RNG seed are
+    fixed and the tile order, lane map and occupancy the set-up measures only permute the launch, so the same
+    arguments give the same frame bit for bit from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = img.cpu().numpy().astype(np.float32, copy=False)
+    idx = dump_sample(a.shape[0] * a.shape[1])
+    if idx is not None:
+        a = a.reshape(-1, 4)[idx]
+    frame, codes = split_nonfinite(a)
+    np.save(os.path.join(out_dir, "frame.npy"), np.ascontiguousarray(frame))
+    np.save(os.path.join(out_dir, "frame_nonfinite.npy"), np.ascontiguousarray(codes))
 
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "fullframe_oracle.json")
@@ -1073,9 +1129,17 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc pass (roofline.frac = null)")
-    ap.add_argument("--pmc-dir", default=None, help="keep the PMC pass's rocprofv3 output here")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the bit-exact checks (--check), frame 0's traversal counts, the "
+                         "roofline with its rocprofv3 --pmc pass, and the CPU baseline (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's frame (what a caller of rt_render receives; N > 1: "
+                         "rank 0's gathered frame) as DIR/frame.npy, float32 [H, W, 4], with 0 for a non-finite component, and "
+                         "DIR/frame_nonfinite.npy, float32 [H, W], coding where those were (0 = none); over 60 MB in all: a "
+                         "fixed seeded sample of the pixels, [n, 4] and [n]")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 --pmc pass (roofline.frac = null)")
+    ap.add_argument("--pmc-dir", default=None, help="--full: keep the PMC pass's rocprofv3 output here")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the frame the CPU baseline renders (0 = auto)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
@@ -1113,9 +1177,9 @@ def main():
     ap.add_argument("--rank-deadline", type=float, default=480.0,
                     help="N > 1: seconds after which a still-running job is killed whole (0 = none)")
     ap.add_argument("--check", dest="check", action="store_true", default=True,
-                    help="(default) after timing, rank 0 re-renders the same frames unsharded, plain tile order, "
+                    help="--full (its default): after timing, rank 0 re-renders the same frames unsharded, plain tile order, "
                          "and compares the final frame bit for bit with the timed one (N > 1: the gathered frame)")
-    ap.add_argument("--no-check", dest="check", action="store_false", help="skip the bit-exact check")
+    ap.add_argument("--no-check", dest="check", action="store_false", help="--full: skip the bit-exact check")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_child:  # the CPU baseline's own process (see cpu_baseline_child)
@@ -1123,6 +1187,7 @@ def main():
         return 0
     if args.plan is None:
         args.plan = "cost"
+    args.check = args.check and args.full  # a plain run times the steps and nothing else
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.pmc_child:
         return launch_ranks(args.gpus, deadline_s=args.rank_deadline)
     return run(args)

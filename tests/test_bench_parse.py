@@ -40,3 +40,45 @@ def test_read_pmc_pass_picks_the_production_variant(tmp_path):
 
 def test_read_pmc_pass_empty(tmp_path):
     assert bench.read_pmc_pass(str(tmp_path)) == ({}, None, [])
+
+
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs (CPU part): a frame within the size limit is written whole, bit for bit, as float32,
+    its non-finite components as 0 with their place and kind in frame_nonfinite.npy, so both files are
+    finite and together give the frame back; a larger frame as the same sorted, duplicate-free sample of
+    its pixels on every call."""
+    import numpy as np
+    import torch
+
+    img = torch.arange(9 * 7 * 4, dtype=torch.float32).reshape(9, 7, 4)
+    img[2, 3, 1] = float("nan")
+    img[4, 0, 0], img[4, 0, 3] = float("inf"), float("-inf")
+    img[8, 6, :] = float("nan")
+    bench.dump_outputs(str(tmp_path / "whole"), img)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["frame.npy", "frame_nonfinite.npy"]
+    a = np.load(tmp_path / "whole" / "frame.npy")
+    codes = np.load(tmp_path / "whole" / "frame_nonfinite.npy")
+    assert a.dtype == codes.dtype == np.float32 and a.shape == (9, 7, 4) and codes.shape == (9, 7)
+    assert np.isfinite(a).all() and np.isfinite(codes).all()
+    assert codes[2, 3] == 1 * 4 and codes[4, 0] == 2 + 3 * 64 and codes[8, 6] == 1 + 4 + 16 + 64
+    assert np.count_nonzero(codes) == 3
+    # the two arrays give the frame back: the finite components bit for bit, the others by kind
+    kind = codes.astype(np.int64)[..., None] // 4 ** np.arange(4) % 4
+    back = np.where(kind == 0, a, np.array([0, np.nan, np.inf, -np.inf], dtype=np.float32)[kind])
+    assert np.array_equal(back, img.numpy(), equal_nan=True)
+    assert np.array_equal(a[kind == 0].view(np.uint32), img.numpy()[kind == 0].view(np.uint32)) and (a[kind != 0] == 0).all()
+
+    assert bench.dump_sample(1920 * 1080) is None  # the headline frame (33 + 8 MB) is written whole
+    idx = bench.dump_sample(3840 * 2160)  # config 3's 133 MB frame
+    assert idx.size * 20 + 256 <= 64 * 10 ** 6 and idx.size >= 3840 * 2160 // 4
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < 3840 * 2160
+    assert np.array_equal(idx, bench.dump_sample(3840 * 2160))
+
+    small = bench.dump_sample(63, max_bytes=20 * 20)  # room for 20 of the 63 pixels
+    assert small.size == 20
+    monkeypatch.setattr(bench, "dump_sample", lambda pixels: small)
+    bench.dump_outputs(str(tmp_path / "sample"), img)
+    s = np.load(tmp_path / "sample" / "frame.npy")
+    sc = np.load(tmp_path / "sample" / "frame_nonfinite.npy")
+    assert s.dtype == np.float32 and s.shape == (20, 4) and sc.shape == (20,)
+    assert np.array_equal(s, a.reshape(-1, 4)[small]) and np.array_equal(sc, codes.reshape(-1)[small])

@@ -310,13 +310,13 @@ def test_rccl_gather_one_rank(rt):
 
 
 def test_bench_two_ranks_without_launcher(tmp_path):
-    """bench.py --gpus 2 --backend gloo --same-device --check: bench starts both ranks itself
+    """bench.py --gpus 2 --backend gloo --same-device --full: bench starts both ranks itself
     (no torchrun), deals tiles by the probe's costs, gathers, and rank 0's frame equals an
     unsharded render of the same frames bit for bit.  --lane-refine 0: the model's lane map is
     rendered as planned (with refinement, config 1's tiny frame keeps the plain tile order, which
     the default bench runs cover)."""
     cmd = [sys.executable, os.path.join(T.ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device",
-           "--check", "--steps", "2", "--warmup", "1", "--config", "cfg1", "--no-cpu-baseline", "--lane-refine", "0"]
+           "--full", "--steps", "2", "--warmup", "1", "--config", "cfg1", "--no-cpu-baseline", "--lane-refine", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

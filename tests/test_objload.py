@@ -4,8 +4,10 @@ the reference's Scene::AddLoadedScene (RayTracing/Scene.cpp:75-132) receives the
 positions, vertex order and faces bit for bit, and normals within a few ulps (the smoothing
 sum's order follows assimp's internal sort of tied SpatialSort entries, not reproduced).
 
-Reads the OBJ from /root/reference (the survey container only; skipped elsewhere).  CPU only.
+The OBJ is the reference's own file, kept xz-compressed as tests/golden/stanford-bunny.obj.xz
+(tools/make_assets.py fixtures) and unpacked into the test's temporary directory.  CPU only.
 """
+import lzma
 import os
 
 import numpy as np
@@ -13,8 +15,15 @@ import pytest
 
 import rt_testlib as T
 
-OBJ = "/root/reference/data/stanford-bunny.obj"
-pytestmark = pytest.mark.skipif(not os.path.exists(OBJ), reason="reference data not present")
+OBJ_XZ = os.path.join(T.GOLDEN, "stanford-bunny.obj.xz")
+
+
+@pytest.fixture
+def obj_path(tmp_path):
+    path = tmp_path / "stanford-bunny.obj"
+    with lzma.open(OBJ_XZ) as src:
+        path.write_bytes(src.read())
+    return str(path)
 
 
 def _scene(rt, path):
@@ -27,10 +36,10 @@ def _scene(rt, path):
     return v, f
 
 
-def test_obj_matches_assimp_import():
+def test_obj_matches_assimp_import(obj_path):
     rt = T.load_rt()
     va, fa = _scene(rt, os.path.join(T.ROOT, "assets", "bunny_mesh.bin"))
-    vo, fo = _scene(rt, OBJ)
+    vo, fo = _scene(rt, obj_path)
     assert va.shape == vo.shape and fa.shape == fo.shape
     # AddLoadedScene: the indexed (smooth) copy first, then the flat copies
     assert np.array_equal(fa, fo)

@@ -34,7 +34,7 @@ for v in ${VARS:-current}; do
       rc=$?
       echo "rep $rep $v $c [$a] exit $rc: $(grep '"max_ms"' $log | python3 -c 'import sys,json; print([(d["n"], d.get("lane"), d["max_ms"]) for d in map(json.loads, sys.stdin)])' 2>&1 | tail -1)"
     else
-      timeout -k 10 ${TIMEOUT:-300} python bench.py --config $c --no-pmc --no-cpu-baseline --steps ${STEPS:-10} --warmup 2 $a > $log 2>&1
+      timeout -k 10 ${TIMEOUT:-300} python bench.py --config $c --full --no-pmc --no-cpu-baseline --steps ${STEPS:-10} --warmup 2 $a > $log 2>&1
       rc=$?
       echo "rep $rep $v $c [$a] exit $rc: $(tail -1 $log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); p=d.get("plan") or {}; print(d["ms_per_step"], d["roofline"]["kernel_ms"], "check", d.get("check_equal"), "occ", (p.get("occupancy") or {}).get("waves_per_simd"), "refine", ((p.get("lanes") or {}).get("refine") or {}).get("frame_ms"))' 2>&1 | tail -1)"
     fi

@@ -8,6 +8,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 LIB=cuda-raytracing_amd/librt_hip.so
 cp $LIB /tmp/current.so.bak
+ARGS="--full ${ARGS:-}"  # the PMC pass and the check are legs of a --full run
 n=0
 for rep in $(seq 1 ${REPS:-2}); do
 for c in ${CFGS:-cfg2}; do

@@ -10,6 +10,7 @@ timeout -k 10 900 python -u -m pytest tests -v -m gpu -x --timeout 300 --timeout
 rc=$?; echo "pytest -m gpu exit $rc"; tail -5 gpurun_out/pytest_gpu.log; stop_if_fatal $rc pytest
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1
 rc=$?; echo "smoke exit $rc"; tail -3 gpurun_out/smoke.log; stop_if_fatal $rc smoke
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # with the checks, the roofline and the CPU baseline
 timeout -k 10 300 python bench.py --steps ${BENCH_STEPS:-5} --warmup 2 ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1
 rc=$?; echo "bench exit $rc"; tail -3 gpurun_out/bench.log; stop_if_fatal $rc bench
 if [ -n "${PROFILE:-}" ]; then

@@ -151,7 +151,33 @@ def make_sky():
     print("sky", width, mips)
 
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
+
+
+def make_test_fixtures():
+    """The two input files themselves as test data (tests/test_objload.py, tests/test_sky_input.py), so the
+    readers are tested where the reference is absent:
+    * tests/golden/stanford-bunny.obj.xz -- data/stanford-bunny.obj, xz-compressed;
+    * tests/golden/sunset_dds_mips.npz -- data/sunset_uncompressed.dds without its level-0 texels (those are
+      assets/sunset_cube128.bin): the 128-byte header and, per face, the bytes of mips 1-7.  The test puts the
+      file together again from the two."""
+    import lzma
+
+    obj = open(os.path.join(REF, "data/stanford-bunny.obj"), "rb").read()
+    with open(os.path.join(GOLDEN, "stanford-bunny.obj.xz"), "wb") as fh:
+        fh.write(lzma.compress(obj, preset=9 | lzma.PRESET_EXTREME))
+    b = open(os.path.join(REF, "data/sunset_uncompressed.dds"), "rb").read()
+    body = np.frombuffer(b, dtype=np.uint8, offset=128).reshape(6, -1)
+    level0 = 16 * 128 * 128
+    np.savez_compressed(os.path.join(GOLDEN, "sunset_dds_mips.npz"), header=np.frombuffer(b, dtype=np.uint8, count=128),
+                        mips=body[:, level0:])
+    print("fixtures", len(obj), body.shape)
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["fixtures"]:
+        make_test_fixtures()
+        sys.exit(0)
     os.makedirs(OUT, exist_ok=True)
     make_sky()
     make_bunny()
