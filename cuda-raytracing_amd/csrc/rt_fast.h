@@ -26,6 +26,12 @@
 namespace rtfast {
 
 constexpr int BIG = 8;     // leaves above this size wait for the wave (and have pair records)
+// MODE bit 7, the fixed-policy ("lean") production variants: RT_TUNE is the compile-time constant 0 and
+// every mirror array the variant uses is present (17: spairs, pairs, quads, units, tris; a leaf-tree mode
+// would add tree, ltris, flat, face_leaf -- none is built: rt_fast_lean.hip), so neither the knobs nor the
+// fallbacks for a missing array are compiled in.  rt_kernel.hip launch_fast routes a frame here only when
+// both hold.
+constexpr int LEAN_BIT = 128;
 constexpr int WAVE = 64;  // lane stride of the LDS stack
 
 using rtm::f3;
@@ -154,23 +160,22 @@ __device__ __forceinline__ float4 ldc(ConstF4 p, uint32_t i) {
     return make_float4(v.x, v.y, v.z, v.w);
 }
 
-// The traversal stack of one lane: node indices, the first SL entries in LDS (lane stride WGL, the
+// The traversal stack of one lane: node indices, the first SL entries in LDS (lane stride WAVE, the
 // workgroup's lanes), deeper ones in a private per-lane array (scratch memory).  Deep stacks are rare -- no
 // ray of a config-2 frame goes past 15 entries -- so a 16-entry LDS stack (4 KB per wave) costs nothing
 // and leaves registers, not LDS, as the occupancy limit.
-template <int SL, int WGL = WAVE>
+template <int SL>
 struct Stack {
     static constexpr int LDS_ENTRIES = SL;
-    static constexpr int LANES = WGL;  // lanes sharing the LDS rows (one wave, or a wave pair: trace)
+    static constexpr int LANES = WAVE;  // lanes sharing the LDS rows (the workgroup is one wave)
     // A lane's stack pointer is ENCODED as the byte offset of its next entry from lane 0's entry 0:
-    // sp = 4 * column + 4 WGL * depth (entry i of column l at lds0[l + i * WGL]).  The LDS address of an entry
+    // sp = 4 * column + 4 WAVE * depth (entry i of column l at lds0[l + i * WAVE]).  The LDS address of an entry
     // is then lds0 + sp, one uniform base and the pointer the lane already holds: no per-lane column
     // address to keep live beside it (the 7-wave build spilled that address and reloaded it on every pop).
-    // The column is the workgroup lane that started the ray; a ray handed to another lane of the workgroup
-    // (wave pairs, trace) keeps its column and so its entries.
+    // The column is the lane that started the ray.
     uint32_t* lds0;  // column 0's entry 0 (workgroup-uniform)
     uint32_t* ovf;   // this lane's entries SL, SL + 1, ...
-    static constexpr int STEP = 4 * WGL;  // sp per entry
+    static constexpr int STEP = 4 * WAVE;  // sp per entry
     static __device__ __forceinline__ int depth(int sp) { return (int)((uint32_t)sp / (uint32_t)STEP); }  // sp >= 0: a shift
     static __device__ __forceinline__ int column(int sp) { return (sp & (STEP - 1)) >> 2; }
     static __device__ __forceinline__ int empty(int col) { return 4 * col; }  // sp of an empty stack
@@ -1114,7 +1119,7 @@ __device__ __forceinline__ bool pop_d(const float4* nodes4, uint32_t* D, const S
 // 22.2 vs 20.6 ms, the extra divergence costs more than the saved iterations.)
 // DEF (deferred big leaves, D non-null): a big leaf the lane reaches as its first is deferred at once
 // (defer_leaf), so the lane steps on instead of waiting for the wave's big-leaf round.
-template <bool STATS, bool SCR = false, bool DEF = false, class S, class C>
+template <bool STATS, bool SCR = false, bool DEF = false, bool LEAN = false, class S, class C>
 __device__ __forceinline__ bool small_step(const float4* nodes4, const float4* tris, const float4* spairs, const S& stk,
                                            const Ray& R, Hit& h, Trav& T, C& c, const float4* pairs = nullptr,
                                            uint32_t* D = nullptr) {
@@ -1128,7 +1133,7 @@ __device__ __forceinline__ bool small_step(const float4* nodes4, const float4* t
         }
     }
     if (T.count > 0) {
-        if (!STATS && spairs) {
+        if (!STATS && (LEAN || spairs)) {
             // two triangles per packed pair record (mirror.h spairs), in leaf order
             for (uint32_t i = T.first; i < T.first + T.count; i += 2) pair_test(R, ld_pair(spairs, i), h);
         } else {
@@ -1154,7 +1159,8 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
                                           const float4* ltris, const float4* flat, uint32_t* scratch, uint32_t tune,
                                           unsigned long long big, bool waiting,
                                           const Ray& R, Hit& h, const Trav& T, C& c) {
-    if ((MODE & 4) && tree) {  // MODE bit 2: the scene has leaf trees
+    constexpr bool LEAN = (MODE & LEAN_BIT) != 0;  // fixed policy: tune == 0, every mirror array present (trace)
+    if ((MODE & 4) && (LEAN || tree)) {  // MODE bit 2: the scene has leaf trees
         // lanes at leaves with a leaf tree (mirror.h: lead record pf == 2) walk it on their own
         bool at_tree = false;
         uint32_t root = 0;
@@ -1165,7 +1171,7 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
         }
         const unsigned long long mt = __ballot(at_tree);
         if (mt) {
-            if (!STATS && flat && (tune & 0x40000000u) == 0)  // RT_TUNE bit 30: per-lane walk instead
+            if (!STATS && (LEAN || flat) && (tune & 0x40000000u) == 0)  // RT_TUNE bit 30: per-lane walk instead
             {
                 const unsigned long long tt0 = (MODE & 8) ? __builtin_amdgcn_s_memtime() : 0;
                 coop_tree<(MODE & 8) != 0>(tris, tree, ltris, flat, mt, root, R, h, T, scratch, tune, c);
@@ -1189,7 +1195,7 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
         // the first record of a big leaf says where its pairs are, the second where its twin quads are (mirror.h)
         const f4v lead = ((ConstF4)(tris + 3 * (size_t)f0))[2];
         const uint32_t k = (uint32_t)__popcll(big);
-        if (!STATS && (MODE & 3) < 2 && quads && (__float_as_uint(lead.w) & 1u)) {
+        if (!STATS && (MODE & 3) < 2 && (LEAN || quads) && (__float_as_uint(lead.w) & 1u)) {
             // the second record: the leaf's first quad and quad count, the third: first unit and count
             const f4v l2 = ((ConstF4)(tris + 3 * (size_t)f0 + 3))[2];
             const f4v l3 = ((ConstF4)(tris + 3 * (size_t)f0 + 6))[2];
@@ -1222,7 +1228,7 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
                 return waiting;
             }
         }
-        if (!STATS && (MODE & 3) < 2 && pairs && (__float_as_uint(lead.w) & 1u)) {
+        if (!STATS && (MODE & 3) < 2 && (LEAN || pairs) && (__float_as_uint(lead.w) & 1u)) {
             const float4* lp = pairs + 5 * (size_t)__float_as_uint(lead.z);
             const uint32_t np = (c0 + 1u) / 2u, chunks = (np + 63u) / 64u;
             // cost model (VALU instructions per pair ~40): cooperative ~ k * (40 * chunks + 60),
@@ -1459,253 +1465,6 @@ __device__ __forceinline__ void lone_traverse(const float4* nodes4, const float4
     }
 }
 
-// ---------------------------------------------------------------------------------------
-// Wave pairs (RT_PAIR = K, experiment: two waves per workgroup).  A wave's traversal ends with a tail: a
-// few lanes still stepping while the rest wait (config 2, 7 waves per SIMD: small-step iterations with 1-4
-// active lanes are 13 % of wave cycles, lone-lane traversals 4 %), and every one of those iterations is
-// issued for 64 lanes.  Here a wave whose small phase is down to <= K rays (no lane waiting at a big leaf)
-// hands them to the other wave of its workgroup, which runs them in its FREE lanes -- lanes with no segment
-// this call (their pixel is done), whose ray, hit and traversal registers are dead -- beside its own rays;
-// the donor sleeps until their hits come back.  Exact by construction: a ray's traversal is the same
-// sequence of steps whichever lane runs it; its LDS stack stays where it is (Stack: the stack pointer
-// carries the ray's column), only rays whose entries all live in LDS move, and an adopted ray finishes where
-// it was adopted.  The exchange goes through an LDS mailbox: word 0 the protocol word, then field f of ray k
-// at 1 + f PAIR_K + k of the posting wave's region (21 fields: o, d, nd, 1/d, fast, hit, first, count, sp), the hit coming back in its own
-// fields.  Protocol word: bit w = wave w is in trace and may be handed rays, bits 8 + 8w.. = its free lanes,
-// bits 24-25 = phase (EMPTY, POSTED, ADOPTED, DONE), bit 26 = the posting wave, bits 27-31 = ray count.  Only
-// lane 0 of a wave changes it (compare-and-swap); the posting wave waits for DONE, the other one adopts a
-// POSTED hand-over before it may leave trace, so nothing is left behind and nothing waits on a wave that
-// cannot answer.
-// ---------------------------------------------------------------------------------------
-#if defined(RT_PAIR)
-constexpr int PAIR_K = RT_PAIR;
-constexpr uint32_t PH_EMPTY = 0u, PH_POSTED = 1u, PH_ADOPTED = 2u, PH_DONE = 3u;
-constexpr int PAIR_FIELDS = 21;
-constexpr int PAIR_MAIL_WORDS = 1 + 2 * PAIR_FIELDS * PAIR_K;  // the protocol word + one region per posting wave
-// the region wave w posts its rays in (and gets their hits back in): a wave never writes into the region of a
-// hand-over it did not post
-__device__ __forceinline__ uint32_t* pair_region(uint32_t* mail, uint32_t w) { return mail + w * PAIR_FIELDS * PAIR_K; }
-__device__ __forceinline__ uint32_t pair_phase(uint32_t st) { return (st >> 24) & 3u; }
-__device__ __forceinline__ uint32_t pair_free(uint32_t st, uint32_t w) { return (st >> (8u + 8u * w)) & 127u; }
-__device__ __forceinline__ uint32_t pair_load(uint32_t* mail) {
-    return (uint32_t)__builtin_amdgcn_readfirstlane(
-        (int)__hip_atomic_load(mail, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-}
-// lane 0 replaces the protocol word by f(old) while f accepts old; returns (wave-uniform) whether it did
-template <class F>
-__device__ __forceinline__ bool pair_update(uint32_t* mail, F f) {
-    int ok = 0;
-    if ((threadIdx.x & 63u) == 0) {
-        uint32_t old = __hip_atomic_load(mail, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP), nw;
-        while (f(old, nw)) {
-            if (__hip_atomic_compare_exchange_strong(mail, &old, nw, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE,
-                                                     __HIP_MEMORY_SCOPE_WORKGROUP)) {
-                ok = 1;
-                break;
-            }
-        }
-    }
-    return __builtin_amdgcn_readfirstlane(ok) != 0;
-}
-__device__ __forceinline__ void pair_put_hit(uint32_t* mail, int k, const Hit& h) {
-    uint32_t* m = mail + 1 + k;
-    m[13 * PAIR_K] = __float_as_uint(h.best), m[14 * PAIR_K] = (uint32_t)h.kind, m[15 * PAIR_K] = h.id;
-    m[16 * PAIR_K] = __float_as_uint(h.bx), m[17 * PAIR_K] = __float_as_uint(h.by);
-}
-__device__ __forceinline__ void pair_get_hit(const uint32_t* mail, int k, Hit& h) {
-    const uint32_t* m = mail + 1 + k;
-    h.best = __uint_as_float(m[13 * PAIR_K]), h.kind = (int)m[14 * PAIR_K], h.id = m[15 * PAIR_K];
-    h.bx = __uint_as_float(m[16 * PAIR_K]), h.by = __uint_as_float(m[17 * PAIR_K]);
-}
-__device__ __forceinline__ void pair_put_ray(uint32_t* mail, int k, const Ray& R, const Hit& h, const Trav& T) {
-    uint32_t* m = mail + 1 + k;
-    const float v[12] = {R.o.x, R.o.y, R.o.z, R.d.x, R.d.y, R.d.z, R.nd.x, R.nd.y, R.nd.z, R.r.x, R.r.y, R.r.z};
-    for (int f = 0; f < 12; f++) m[f * PAIR_K] = __float_as_uint(v[f]);
-    m[12 * PAIR_K] = R.fast ? 1u : 0u;
-    pair_put_hit(mail, k, h);
-    m[18 * PAIR_K] = T.first, m[19 * PAIR_K] = T.count, m[20 * PAIR_K] = (uint32_t)T.sp;
-}
-__device__ __forceinline__ void pair_get_ray(const uint32_t* mail, int k, Ray& R, Hit& h, Trav& T) {
-    const uint32_t* m = mail + 1 + k;
-    R.o = rtm::mk(__uint_as_float(m[0]), __uint_as_float(m[PAIR_K]), __uint_as_float(m[2 * PAIR_K]));
-    R.d = rtm::mk(__uint_as_float(m[3 * PAIR_K]), __uint_as_float(m[4 * PAIR_K]), __uint_as_float(m[5 * PAIR_K]));
-    R.nd = rtm::mk(__uint_as_float(m[6 * PAIR_K]), __uint_as_float(m[7 * PAIR_K]), __uint_as_float(m[8 * PAIR_K]));
-    R.r = rtm::mk(__uint_as_float(m[9 * PAIR_K]), __uint_as_float(m[10 * PAIR_K]), __uint_as_float(m[11 * PAIR_K]));
-    R.fast = m[12 * PAIR_K] != 0u;
-    pair_get_hit(mail, k, h);
-    T.first = m[18 * PAIR_K], T.count = m[19 * PAIR_K], T.sp = (int)m[20 * PAIR_K];
-}
-#endif
-
-#if defined(RT_GROUP)
-// ---------------------------------------------------------------------------------------
-// Group traversal (experiment, -DRT_GROUP = most rays): lone_traverse for 2-4 rays at
-// once.  When the small phase is down to n = 2..RT_GROUP rays and every other lane is done (no lane waits at a
-// big leaf), the wave splits into n groups: each ray's own lane (its OWNER) plus the done lanes dealt round
-// robin (MEMBERS; their ray and traversal registers are dead, their hit is not and is left alone).  Every
-// lane of a group holds the group's ray (copied once from the owner), current node, depth and closest
-// distance, and runs the inner steps' filtered-exact decisions itself; the group's stack is spread over its
-// members (member e holds entry e with its filtered tmin, as in lone_traverse), so a pop is one ballot and
-// the highest passing member of the group; the owner alone tests a small leaf (pair_test, its own hit) and
-// the group's distance follows by a permute.  Any group reaching a big leaf, or a push its members cannot
-// hold, ends group mode for all: stacks go back to the owners' LDS columns, the big-leaf rounds take over.
-// The same steps in the same order per ray: bit-exact by construction.
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t bperm(uint32_t v, int src) {
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)v);
-}
-__device__ __forceinline__ float bpermf(float v, int src) { return __uint_as_float(bperm(__float_as_uint(v), src)); }
-__device__ __forceinline__ uint32_t rank_in(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-#if defined(RT_GROUP_CALL)  // a real call: the trace loop's register allocation stays the production one
-#define RT_GROUP_INLINE __attribute__((noinline))
-#else
-#define RT_GROUP_INLINE __forceinline__
-#endif
-template <class S>
-__device__ RT_GROUP_INLINE void group_traverse(const float4* nodes4, const float4* spairs, const S& stk,
-                                               unsigned long long mS, Ray& R, Hit& h, Trav& T, bool& active) {
-    constexpr int SL = S::LDS_ENTRIES;
-    const int lane = (int)(threadIdx.x & 63u);
-    const uint32_t n = (uint32_t)__popcll(mS);
-    const bool owner = ((mS >> lane) & 1ull) != 0;
-    const uint32_t mrank = rank_in(~mS);
-    const uint32_t gid = owner ? rank_in(mS) : mrank % n;
-    const int eidx = owner ? -1 : (int)(mrank / n);
-    const int cap = min((int)((64u - n) / n), SL);  // entries every group's members can hold, all in LDS at exit
-    // the owners' lanes (wave-uniform), then this lane's group owner and group mask
-    unsigned long long rest = mS, gm = 0;
-    int ol = lane;
-    for (uint32_t k = 0; k < n; k++) {
-        const int lk = __ffsll((long long)rest) - 1;
-        rest &= rest - 1;
-        const unsigned long long mk = __ballot(gid == k);
-        if (gid == k) ol = lk, gm = mk;
-    }
-    // the group's ray, node, depth and closest distance from its owner (members' ray registers are dead)
-    R.o = rtm::mk(bpermf(R.o.x, ol), bpermf(R.o.y, ol), bpermf(R.o.z, ol));
-    R.d = rtm::mk(bpermf(R.d.x, ol), bpermf(R.d.y, ol), bpermf(R.d.z, ol));
-    R.nd = rtm::mk(bpermf(R.nd.x, ol), bpermf(R.nd.y, ol), bpermf(R.nd.z, ol));
-    R.r = rtm::mk(bpermf(R.r.x, ol), bpermf(R.r.y, ol), bpermf(R.r.z, ol));
-    R.fast = bperm(R.fast ? 1u : 0u, ol) != 0u;
-    uint32_t cf = bperm(T.first, ol), cc = bperm(T.count, ol);
-    const int osp = (int)bperm((uint32_t)T.sp, ol);
-    const int ocol = S::column(osp);
-    int gd = S::depth(osp);
-    float gb = bpermf(h.best, ol);
-    uint32_t* const col = stk.lds0 + ocol;
-    // member e: entry e of its group's stack, with its filtered tmin (lone_traverse's entry state)
-    uint32_t e_idx = 0, e_first = 0, e_count = 0;
-    float e_tmin = 0.0f;
-    bool e_exact = false;
-    if (eidx >= 0 && eidx < gd) {
-        e_idx = col[eidx * S::LANES];
-        const float4 lo = ldo(nodes4, 2 * e_idx), hi = ldo(nodes4, 2 * e_idx + 1);
-        float tx;
-        if (R.fast) {
-            slab_approx(R, lo, hi, &e_tmin, &tx);
-        } else {
-            slab_exact(R, lo, hi, &e_tmin, &tx);
-            e_exact = true;
-        }
-        e_first = __float_as_uint(hi.z), e_count = __float_as_uint(hi.w);
-    }
-    bool gdone = false;  // this lane's group: its ray's traversal is over
-    for (;;) {
-        bool do_pop = false, leave = false;
-        if (!gdone) {
-            if (cc == 0) {
-                if (gd >= cap) {
-                    leave = true;  // a push might not fit the members: back to per-lane steps
-                } else {
-                    const float4 l0 = ldo(nodes4, 2 * cf), l1 = ldo(nodes4, 2 * cf + 1);
-                    const float4 r0 = ldo(nodes4, 2 * cf + 2), r1 = ldo(nodes4, 2 * cf + 3);
-                    float tl = 0.0f, tlx = 0.0f, tr = 0.0f, trx = 0.0f;
-                    int okl = UNSURE, okr = UNSURE, rlt = UNSURE;
-                    if (R.fast) {
-                        slab_approx(R, l0, l1, &tl, &tlx);
-                        slab_approx(R, r0, r1, &tr, &trx);
-                        okl = classify_ok(tl, tlx);
-                        okr = classify_ok(tr, trx);
-                        rlt = okr == YES ? classify_lt(tr, gb) : NO;
-                    }
-                    bool exact_l = false;
-                    if (okl == UNSURE || okr == UNSURE || rlt == UNSURE) {
-                        slab_exact(R, l0, l1, &tl, &tlx);
-                        slab_exact(R, r0, r1, &tr, &trx);
-                        okl = (tlx >= tl && tlx > 0.0f) ? YES : NO;
-                        okr = (trx >= tr && trx > 0.0f) ? YES : NO;
-                        rlt = (okr == YES && tr < gb) ? YES : NO;
-                        exact_l = true;
-                    }
-                    if (rlt == YES) {
-                        if (okl == YES) {
-                            if (eidx == gd) e_idx = cf, e_tmin = tl, e_exact = exact_l, e_first = __float_as_uint(l1.z),
-                                            e_count = __float_as_uint(l1.w);
-                            gd++;
-                        }
-                        cf = __float_as_uint(r1.z), cc = __float_as_uint(r1.w);
-                    } else {
-                        bool llt = false;
-                        if (okl == YES) {
-                            int cl = exact_l ? (tl < gb ? YES : NO) : classify_lt(tl, gb);
-                            if (cl == UNSURE) {
-                                float te, tx;
-                                slab_exact(R, l0, l1, &te, &tx);
-                                cl = te < gb ? YES : NO;
-                            }
-                            llt = cl == YES;
-                        }
-                        if (llt) cf = __float_as_uint(l1.z), cc = __float_as_uint(l1.w);
-                        else do_pop = true;
-                    }
-                }
-            } else if (cc <= (uint32_t)BIG) {
-                if (owner)  // the small leaf, in leaf order, on the owner's own hit
-                    for (uint32_t i = cf; i < cf + cc; i += 2) pair_test(R, ld_pair(spairs, i), h);
-                do_pop = true;
-            } else {
-                leave = true;  // a big leaf: the wave's big-leaf rounds
-            }
-        }
-        gb = bpermf(h.best, ol);  // (owners' distances; members' own hits untouched)
-        if (__ballot(leave)) break;
-        // pops: members holding live entries test them; the group continues at its highest passing entry
-        int cl = NO;
-        if (!gdone && do_pop && eidx >= 0 && eidx < gd) {
-            cl = e_exact ? (e_tmin < gb ? YES : NO) : classify_lt(e_tmin, gb);
-            if (cl == UNSURE) {
-                const float4 lo = ldo(nodes4, 2 * e_idx), hi = ldo(nodes4, 2 * e_idx + 1);
-                float tx;
-                slab_exact(R, lo, hi, &e_tmin, &tx);
-                e_exact = true;
-                cl = e_tmin < gb ? YES : NO;
-            }
-        }
-        const unsigned long long P = __ballot(cl == YES) & gm;
-        const int w = P ? 63 - __clzll((long long)P) : lane;
-        const uint32_t wf = bperm(e_first, w), wc = bperm(e_count, w), we = bperm((uint32_t)eidx, w);
-        if (!gdone && do_pop) {
-            if (P) {
-                cf = wf, cc = wc, gd = (int)we;
-            } else {
-                gdone = true;
-                if (owner) active = false;
-            }
-        }
-        if (!__ballot(!gdone)) break;
-    }
-    // back to per-lane state: the owners of unfinished rays take the group's node and depth, the members
-    // put their entries back into the owner's LDS column (gd <= cap <= the LDS rows)
-    if (!gdone) {
-        if (owner) T.first = cf, T.count = cc, T.sp = S::empty(ocol) + gd * S::STEP;
-        if (eidx >= 0 && eidx < gd) col[eidx * S::LANES] = e_idx;
-    }
-}
-#endif
-
 // BVHRayHit for one lane (`live` = the lane has a segment to trace), every lane of the wave
 // calling.  Small steps run while any lane has one; big leaves wait until every lane is done
 // or waiting at one.  MODE & 3 -- 0: big leaves through pair records (shared-leaf loop and
@@ -1715,109 +1474,24 @@ __device__ RT_GROUP_INLINE void group_traverse(const float4* nodes4, const float
 template <bool STATS, int MODE, class S, class C>
 __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, const float4* pairs,
                                       const float4* tree, const float4* ltris, const float4* flat,
-                                      const float4* spairs, uint32_t tune, const S& stk, uint32_t* scratch,
+                                      const float4* spairs, uint32_t tune_arg, const S& stk, uint32_t* scratch,
                                       Ray& R, Hit& h, bool live, C& c, const float4* quads = nullptr,
-                                      const float4* units = nullptr, const uint32_t* face_leaf = nullptr,
-                                      uint32_t* mail = nullptr) {
+                                      const float4* units = nullptr, const uint32_t* face_leaf = nullptr) {
+    constexpr bool LEAN = (MODE & LEAN_BIT) != 0;
+    const uint32_t tune = LEAN ? 0u : tune_arg;
     Trav T{0, 0, 0};
     bool active = live && trav_begin<STATS>(nodes4, R, h, T, c);
-#if defined(RT_PAIR)
-    // wave pairs (above): the production split-step kernels without leaf trees, screens or refill
-#if defined(RT_PAIR_NOEXCH)  // A/B: the pair workgroups without the exchange
-    constexpr bool PAIR = false;
-#else
-    constexpr bool PAIR = !STATS && (MODE & 8) == 0 && (MODE & 4) == 0 && (MODE & 16) != 0 && (MODE & 32) == 0 &&
-                          (MODE & 64) == 0;
-#endif
-#ifndef RT_PAIR_EVERY
-#define RT_PAIR_EVERY 1  // iterations between two looks at the mailbox
-#endif
-    uint32_t pair_tick = 0;
-    const uint32_t pw = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // this wave of the pair
-    const uint32_t po = 1u - pw;
-    int adopted = -1;         // mail slot of the other wave's ray this lane runs, or -1
-    uint32_t n_adopted = 0;   // rays adopted (wave-uniform)
-    if (PAIR && mail) {       // in trace: may be handed up to (free lanes) rays
-        const uint32_t nfree = min((uint32_t)__popcll(__ballot(!live)), 127u);
-        pair_update(mail, [&](uint32_t o, uint32_t& nw) {
-            nw = (o & ~(127u << (8u + 8u * pw))) | (1u << pw) | (nfree << (8u + 8u * pw));
-            return true;
-        });
-    }
-    auto pair_publish = [&]() {  // every adopted ray done: their hits back, DONE
-        if (adopted >= 0) pair_put_hit(pair_region(mail, po), adopted, h);
-        adopted = -1, n_adopted = 0;
-        pair_update(mail, [](uint32_t o, uint32_t& nw) {
-            nw = (o & ~(3u << 24)) | (PH_DONE << 24);
-            return true;
-        });
-    };
-#endif
     // big-leaf screens (screen_leaf, MODE bit 5): split-step variants for scenes that have them
     constexpr bool scr_on = !STATS && (MODE & 16) != 0 && (MODE & 32) != 0;
     constexpr bool TIMING = (MODE & 8) != 0;
     // deferred big leaves (defer_leaf): production, timing and refill variants, not the screen ones; D = this
-    // lane's words, or null when deferral is off (RT_TUNE bit 24)
-#if defined(RT_DEFER_ALL)  // experiment: every kernel defers (config 2's floor leaf too)
-    constexpr bool DEFER = !STATS && (MODE & 32) == 0;
-#else  // the leaf-tree kernels (config 2's 7-wave kernel spills 53 -> 186 dwords with the deferral compiled in)
+    // lane's words, or null when deferral is off (RT_TUNE bit 24).  Only the leaf-tree kernels defer: config 2's
+    // 7-wave kernel spills 53 -> 186 dwords with the deferral compiled in.
     constexpr bool DEFER = !STATS && (MODE & 32) == 0 && (MODE & 4) != 0;
-#endif
     uint32_t* const D = (DEFER && (tune & (1u << 24)) == 0) ? defer_words<MODE>(scratch) : nullptr;
     if (D) D[0] = DEFER_NONE;
     unsigned long long t0 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
     for (;;) {
-#if defined(RT_PAIR)
-        if (PAIR && mail && (RT_PAIR_EVERY == 1 || (++pair_tick % RT_PAIR_EVERY) == 0)) {
-            const uint32_t st = pair_load(mail);
-            const uint32_t ph = pair_phase(st);
-            if (ph == PH_POSTED && ((st >> 26) & 1u) != pw) {  // rays handed to this wave: free lanes take them
-                const uint32_t n = st >> 27;
-                const bool fr = !live && adopted < 0;
-                const unsigned long long fm = __ballot(fr);
-                const uint32_t k = __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
-                if (fr && k < n) {
-                    pair_get_ray(pair_region(mail, po), (int)k, R, h, T);
-                    adopted = (int)k;
-                    active = true;
-                }
-                n_adopted = n;
-                pair_update(mail, [](uint32_t o, uint32_t& nw) {
-                    nw = (o & ~(3u << 24)) | (PH_ADOPTED << 24);
-                    return true;
-                });
-                continue;
-            }
-            if (n_adopted && !__ballot(adopted >= 0 && active)) pair_publish();
-            const bool mine = active && T.count <= (uint32_t)BIG;  // this wave's small-phase rays
-            const unsigned long long mS = __ballot(mine);
-            const uint32_t nS = (uint32_t)__popcll(mS);
-            if (!n_adopted && ph == PH_EMPTY && nS && nS <= (uint32_t)PAIR_K && mS == __ballot(active) &&
-                ((st >> po) & 1u) && pair_free(st, po) >= nS && !__ballot(mine && S::depth(T.sp) > S::LDS_ENTRIES)) {
-                const uint32_t k = __builtin_amdgcn_mbcnt_hi((uint32_t)(mS >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mS, 0u));
-                if (mine) pair_put_ray(pair_region(mail, pw), (int)k, R, h, T);
-                if (pair_update(mail, [&](uint32_t o, uint32_t& nw) {
-                        if (pair_phase(o) != PH_EMPTY || !((o >> po) & 1u) || pair_free(o, po) < nS) return false;
-                        nw = (o & 0x00ffffffu) | (PH_POSTED << 24) | (pw << 26) | (nS << 27);
-                        return true;
-                    })) {
-                    // (bounded: a protocol error renders wrong pixels -- the parity tests catch those -- instead of
-                    // hanging the device; ~2^22 sleeps is far beyond any traversal)
-                    for (uint32_t spin = 0; pair_phase(pair_load(mail)) != PH_DONE && spin < (1u << 22); spin++)
-                        __builtin_amdgcn_s_sleep(2);
-                    if (mine) {
-                        pair_get_hit(pair_region(mail, pw), (int)k, h);
-                        active = false;
-                    }
-                    pair_update(mail, [](uint32_t o, uint32_t& nw) {
-                        nw = o & 0x00ffffffu;  // EMPTY
-                        return true;
-                    });
-                    continue;
-                }
-            }
-        }
-#endif
         if constexpr ((MODE & 16) != 0) {
             // split small steps: inner-node steps and small-leaf steps run in separate wave
             // iterations (a lane at a small leaf waits until at least half as many lanes are at
@@ -1829,16 +1503,6 @@ __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, 
             const unsigned long long mI = __ballot(inner), mL = __ballot(leafs);
             if (mI | mL) {
                 const uint32_t nI = (uint32_t)__popcll(mI), nL = (uint32_t)__popcll(mL);
-#if defined(RT_GROUP)
-                if constexpr (!STATS && !scr_on && (MODE & 4) == 0) {
-                    const uint32_t ng = nI + nL;
-                    if (ng >= 2 && ng <= (uint32_t)RT_GROUP && (mI | mL) == __ballot(active) && spairs &&
-                        !__ballot((inner || leafs) && S::depth(T.sp) >= min((int)((64u - ng) / ng), S::LDS_ENTRIES))) {
-                        group_traverse(nodes4, spairs, stk, mI | mL, R, h, T, active);
-                        continue;
-                    }
-                }
-#endif
                 if constexpr (!STATS) {
                     // one lane left in the small phase: the whole wave runs its DFS (lone_traverse),
                     // when its stack lives in LDS (RT_TUNE bit 26 turns this off); a lane that must
@@ -1867,23 +1531,13 @@ __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, 
 #ifdef RT_LANE_HIST  // diagnostic build: wave cycles of small-step iterations by active-lane count
                 const unsigned long long th0 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
 #endif
-#ifdef RT_COMBINE_T
-                // few lanes of both kinds: one iteration serves both (their loads overlap; the split
-                // exists to gather lanes per kind, which matters little when both groups are small)
-                if (!scr_on && mI && mL && nI + nL <= (uint32_t)RT_COMBINE_T) {
-                    if (inner || leafs) {
-                        active = small_step<STATS, false, DEFER>(nodes4, tris, spairs, stk, R, h, T, c, nullptr, D);
-                        if (TIMING) c.lane_work++;
-                    }
-                } else
-#endif
                 if (!mI || nL * 4u >= nI * (q + 1u)) {
                     if (leafs) {
-                        active = small_step<STATS, scr_on>(nodes4, tris, spairs, stk, R, h, T, c, pairs);
+                        active = small_step<STATS, scr_on, false, LEAN>(nodes4, tris, spairs, stk, R, h, T, c, pairs);
                         if (TIMING) c.lane_work++;
                     }
                 } else if (inner) {
-                    active = small_step<STATS, false, DEFER>(nodes4, tris, spairs, stk, R, h, T, c, nullptr, D);
+                    active = small_step<STATS, false, DEFER, LEAN>(nodes4, tris, spairs, stk, R, h, T, c, nullptr, D);
                     if (TIMING) c.lane_work++;
                 }
 #ifdef RT_LANE_HIST
@@ -1948,7 +1602,7 @@ __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, 
                     if (__float_as_uint(h.best) == __float_as_uint(bnd)) {  // nothing in the leaf at or below F
                         h.best = __uint_as_float(h1);
                         if (h1 != entry) {  // F came after the leaf: the guard
-                            const uint32_t P = face_leaf ? face_leaf[h.id] : 0xffffffffu;
+                            const uint32_t P = (LEAN || face_leaf) ? face_leaf[h.id] : 0xffffffffu;
                             float tp = INFINITY, tx;
                             if (P < 0xfffffffeu) slab_exact(R, ldo(nodes4, 2 * P), ldo(nodes4, 2 * P + 1), &tp, &tx);
                             if (tp > h.best) {  // (F's leaf unknown: tp = inf, the whole leaf below the entry)
@@ -1975,18 +1629,6 @@ __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, 
                 if (go) active = true;
                 if (__ballot(active)) continue;
             }
-#if defined(RT_PAIR)
-            if (PAIR && mail) {
-                if (n_adopted) pair_publish();
-                // leave trace: no more rays for this wave, unless a hand-over to it is already POSTED
-                if (!pair_update(mail, [&](uint32_t o, uint32_t& nw) {
-                        if (pair_phase(o) == PH_POSTED && ((o >> 26) & 1u) != pw) return false;
-                        nw = o & ~(1u << pw) & ~(127u << (8u + 8u * pw));
-                        return true;
-                    }))
-                    continue;  // adopt it first
-            }
-#endif
             break;
         }
         if (big_round_d<STATS, MODE>(nodes4, D, tris, pairs, quads, units, tree, ltris, flat, scratch, tune, big, active, R, h,

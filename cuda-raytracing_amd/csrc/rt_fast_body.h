@@ -21,10 +21,36 @@
 
 namespace rtk {
 
+// Cold kernel arguments.  The compiler loads every RenderArgs field once at kernel entry and keeps it in a
+// scalar register; the ~50 registers of the fields used only outside rtfast::trace (camera, sky, surface, RNG,
+// shading arrays, frame sizes) do not fit beside the traversal's own, so they were spilled into two vector
+// registers of a loop that is at its vector-register budget and reloaded on every use.  With COLD, arg() and
+// arg3() read such a field from the kernel-argument segment at the place of use instead (a volatile scalar
+// load, so it is not hoisted back to the entry): nothing is carried across the traversal.  The render kernels'
+// only parameter is the RenderArgs, so the segment starts with it.
+typedef const volatile __attribute__((address_space(4))) RenderArgs* KernelArgs;
+template <bool COLD, class T>
+__device__ __forceinline__ T arg(const RenderArgs& a, T RenderArgs::*m) {
+    if constexpr (COLD) return ((KernelArgs)__builtin_amdgcn_kernarg_segment_ptr())->*m;
+    else return a.*m;
+}
+// three consecutive floats at byte offset `off` of the RenderArgs
+template <bool COLD>
+__device__ __forceinline__ rtm::f3 arg3(const RenderArgs& a, size_t off) {
+    if constexpr (COLD) {
+        typedef const volatile __attribute__((address_space(4))) float* KF;
+        typedef const __attribute__((address_space(4))) char* KC;
+        KF p = (KF)((KC)__builtin_amdgcn_kernarg_segment_ptr() + off);
+        return rtm::f3{p[0], p[1], p[2]};
+    } else {
+        return ld3(reinterpret_cast<const float*>(reinterpret_cast<const char*>(&a) + off));
+    }
+}
+
 // ray_color's per-segment tail (main_raytracing.cu:118-158) for the segment whose closest hit is
 // `h`: emission, throughput, the next direction from 4 draws, Russian roulette; or the sky on a
 // miss.  Updates the path (ro, rd, color, thr); returns true when the path ends here.
-template <bool STATS>
+template <bool STATS, bool COLD = false>
 __device__ __forceinline__ bool shade_segment(const RenderArgs& a, const rtfast::Hit& h, rtm::f3& ro, rtm::f3& rd,
                                               const rtm::f3 nd, rtm::Xorwow& rng, rtm::f3& color, rtm::f3& thr,
                                               Counters& c) {
@@ -37,19 +63,20 @@ __device__ __forceinline__ bool shade_segment(const RenderArgs& a, const rtfast:
         rtm::f3 nrm;
         uint32_t mat;
         if (h.kind == 1) {
-            const GeometrySphere& sp = a.spheres[h.id];
+            const GeometrySphere& sp = arg<COLD>(a, &RenderArgs::spheres)[h.id];
             nrm = rtm::divs(rtm::sub(pos, ld3(sp.position)), sp.radius);
             mat = (uint32_t)sp.material;
         } else {
-            const GPUFace f = a.faces[h.id];
+            const GPUFace f = arg<COLD>(a, &RenderArgs::faces)[h.id];
+            const GPUVertex* const vertices = arg<COLD>(a, &RenderArgs::vertices);
             const float bz = (1.0f - h.bx) - h.by;
-            nrm = rtm::normalize(rtm::add(rtm::add(rtm::muls(ld3(a.vertices[f.v0].normal), h.bx),
-                                                   rtm::muls(ld3(a.vertices[f.v1].normal), h.by)),
-                                          rtm::muls(ld3(a.vertices[f.v2].normal), bz)));
+            nrm = rtm::normalize(rtm::add(rtm::add(rtm::muls(ld3(vertices[f.v0].normal), h.bx),
+                                                   rtm::muls(ld3(vertices[f.v1].normal), h.by)),
+                                          rtm::muls(ld3(vertices[f.v2].normal), bz)));
             if (rtm::dot(nd, nrm) >= 0.0f) nrm = rtm::neg(nrm);
             mat = f.material;
         }
-        const GPUMaterial& m = a.materials[mat];
+        const GPUMaterial& m = arg<COLD>(a, &RenderArgs::materials)[mat];
         const float do_spec = (rng.uniform() < m.specular_percent) ? 1.0f : 0.0f;
         color = rtm::add(color, rtm::mul(thr, ld3(m.emissive)));
         const float om = 1.0f - do_spec;
@@ -76,9 +103,11 @@ __device__ __forceinline__ bool shade_segment(const RenderArgs& a, const rtfast:
         }
     } else {
         if (STATS) c.miss++;
-        if (a.sky) {
-            const rtm::f3 dir = rtd::quat_rotate(a.qw, a.qx, a.qy, a.qz, rd);
-            const rtm::f3 cs = rtd::cube_sample(a.sky, a.sky_n, dir);
+        const float* const sky = arg<COLD>(a, &RenderArgs::sky);
+        if (sky) {
+            const rtm::f3 dir = rtd::quat_rotate(arg<COLD>(a, &RenderArgs::qw), arg<COLD>(a, &RenderArgs::qx),
+                                                 arg<COLD>(a, &RenderArgs::qy), arg<COLD>(a, &RenderArgs::qz), rd);
+            const rtm::f3 cs = rtd::cube_sample(sky, arg<COLD>(a, &RenderArgs::sky_n), dir);
             const rtm::f3 cl = rtm::mk(rtm::gmin(rtm::gmax(cs.x, 0.0f), 50.0f), rtm::gmin(rtm::gmax(cs.y, 0.0f), 50.0f),
                                        rtm::gmin(rtm::gmax(cs.z, 0.0f), 50.0f));
             color = rtm::add(color, rtm::mul(thr, cl));
@@ -117,17 +146,15 @@ __device__ __forceinline__ int xcd_block(uint32_t tune) {
 #ifndef RT_LDS_SL
 #define RT_LDS_SL 16  // stack entries in LDS (4 KB per wave)
 #endif
-#if defined(RT_PAIR)  // experiment (rt_fast.h wave pairs): two waves per workgroup, tails handed over
-constexpr int WG_WAVES = 2;
-#else
-constexpr int WG_WAVES = 1;
-#endif
-constexpr int WGL = WG_WAVES * WAVE;  // lanes per workgroup (the LDS stack's column count)
 
 template <int STACK, bool STATS, int MODE>
 __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
-                                                 const rtfast::Stack<(STACK < RT_LDS_SL ? STACK : RT_LDS_SL), WGL>& stk,
-                                                 uint32_t* const scratch, uint32_t* const mail = nullptr) {
+                                                 const rtfast::Stack<(STACK < RT_LDS_SL ? STACK : RT_LDS_SL)>& stk,
+                                                 uint32_t* const scratch) {
+    constexpr bool LEAN = (MODE & rtfast::LEAN_BIT) != 0;  // fixed policy: RT_TUNE is 0 (rt_fast.h LEAN_BIT)
+    // the lean variants read what only the code around `trace` uses from the kernel-argument segment (arg())
+    constexpr bool COLD = LEAN;
+    auto A = [&](auto member) { return arg<COLD>(a, member); };
     if (a.gate && *a.gate != a.gate_value) return;  // foreign scenes: the other tracer renders this frame
     const float4* nodes4 = reinterpret_cast<const float4*>(a.nodes);
     const float4* tris = reinterpret_cast<const float4*>(a.tris);
@@ -138,7 +165,9 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
     // (32-bit slot, no RNG pointer: rng_slot() recomputes it; the alpha sum is the sample count)
     uint32_t slot = 0;  // < 2^32 (rt_render checks slot_count)
     rtm::Xorwow rng{0, 0, 0, 0, 0, 0};
-    auto rng_slot = [&]() { return a.rng + (a.out_shard ? (size_t)slot : (size_t)y * a.width + x); };
+    auto rng_slot = [&]() {
+        return A(&RenderArgs::rng) + (A(&RenderArgs::out_shard) ? (size_t)slot : (size_t)y * A(&RenderArgs::width) + x);
+    };
     auto bind = [&](int k, int tid) {
         const int tile = k >= 0 ? shard_tile(a, k) : -1;
         int lx, ly;
@@ -154,14 +183,13 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
     };
     // entry i of the launch's lane order: the lane map, or slot i (wave i / 64 = 8x8 sub-tile)
     auto bind_entry = [&](long long i) {
-        const long long s = (WG_WAVES > 1 && i >= a.entry_count) ? -1 : a.lane_slots ? (long long)a.lane_slots[i] : i;
+        const long long s = a.lane_slots ? (long long)a.lane_slots[i] : i;
         const bool ok = s >= 0 && s < a.slot_count;  // a bad map entry renders nothing
         bind(ok ? (int)(s >> 8) : -1, (int)(s & 255));
     };
     // one 64-lane workgroup per 8x8 sub-tile: tile k = lb / 4, sub-tile lb % 4
-    // (wave pairs: the two waves of workgroup g take sub-tiles 2g, 2g + 1)
     const int lane = (int)(threadIdx.x & 63u);
-    const int lb = xcd_block(a.tune) * WG_WAVES + (WG_WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0);
+    const int lb = xcd_block(LEAN ? 0u : a.tune);
     bind_entry((long long)lb * WAVE + lane);
     if (a.lane_slots && lb < a.priority_waves) __builtin_amdgcn_s_setprio(3);  // the frame's long waves
     // Refill (rt_render_params.refill_lanes): the grid holds only as many waves as fit the GPU at
@@ -171,7 +199,7 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
     // Waves that start less than half full (split waves of a lane plan) are not refilled.
     constexpr bool REFILL = (MODE & 64) != 0;  // refill is compiled into its own kernel variants only
     bool drained = !REFILL || a.queue_head == nullptr || __popcll(__ballot(pixel)) < 32;
-    const long long qbase = (long long)gridDim.x * WGL;
+    const long long qbase = (long long)gridDim.x * WAVE;
     Counters c;
     const rtm::f3 cam_o = ld3(a.cam.origin), cam_h = ld3(a.cam.horizontal), cam_v = ld3(a.cam.vertical),
                   cam_ll = ld3(a.cam.lower_left_corner);
@@ -179,12 +207,17 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
     int sample = 0, bounce = 0;
     bool path = false;
     rtm::f3 ro = cam_o, rd = cam_o, color = rtm::mk(0, 0, 0), thr = rtm::mk(1, 1, 1);
-    const bool scene_fast = a.scene_fast != 0;
+    // a camera vector at a sample's start: the value loaded above, or (COLD) the argument itself again
+    auto cam = [&](const rtm::f3& loaded, size_t off) {
+        if constexpr (COLD) return arg3<true>(a, offsetof(RenderArgs, cam) + off);
+        else return loaded;
+    };
     const unsigned long long t_start = (MODE & 8) ? __builtin_amdgcn_s_memtime() : 0;
     // wave_clock and the per-wave (start, end) diagnostics use the device's constant 100 MHz clock
     // (s_memrealtime): one time base for every wave, also for a wave saved and restored by another
     // process sharing the GPU (the shader-cycle counter s_memtime is not)
-    const unsigned long long rt_start = (a.wave_clock || ((MODE & 8) && (a.tune & 2048u))) ? __builtin_amdgcn_s_memrealtime() : 0;
+    const bool wave_times = (MODE & 8) && !LEAN && (a.tune & 2048u);  // RT_TUNE bit 11 (timing frames)
+    const unsigned long long rt_start = (a.wave_clock || wave_times) ? __builtin_amdgcn_s_memrealtime() : 0;
 
 #ifdef RT_LIVE_HIST
     unsigned long long lh_t = 0;
@@ -214,19 +247,22 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
             }
         }
         if (pixel && !path) {
-            if (sample < a.spp) {
+            if (sample < A(&RenderArgs::spp)) {
                 // main_raytracing.cu:190: uv = (pixel + vec2(rng(), rng())) / vec2(W, H), u first
                 const float ru = rng.uniform();
                 const float rv = rng.uniform();
-                const float uvx = ((float)x + ru) / (float)a.width;
-                const float uvy = ((float)y + rv) / (float)a.height;
-                ro = cam_o;  // GPUCamera::GetRay (GPUScene.h:13), not normalized
-                rd = rtm::sub(rtm::add(rtm::add(cam_ll, rtm::muls(cam_h, uvx)), rtm::muls(cam_v, uvy)), cam_o);
+                const float uvx = ((float)x + ru) / (float)A(&RenderArgs::width);
+                const float uvy = ((float)y + rv) / (float)A(&RenderArgs::height);
+                const rtm::f3 co = cam(cam_o, offsetof(GPUCamera, origin)), ch = cam(cam_h, offsetof(GPUCamera, horizontal)),
+                              cv = cam(cam_v, offsetof(GPUCamera, vertical)),
+                              cl = cam(cam_ll, offsetof(GPUCamera, lower_left_corner));
+                ro = co;  // GPUCamera::GetRay (GPUScene.h:13), not normalized
+                rd = rtm::sub(rtm::add(rtm::add(cl, rtm::muls(ch, uvx)), rtm::muls(cv, uvy)), co);
                 color = rtm::mk(0, 0, 0);
                 thr = rtm::mk(1, 1, 1);
                 bounce = 0;
                 path = true;
-                if (a.bounces == 0) {  // an empty bounce loop: the sample contributes (0,0,0,1)
+                if (A(&RenderArgs::bounces) == 0) {  // an empty bounce loop: the sample contributes (0,0,0,1)
                     sample++;
                     path = false;
                     continue;
@@ -234,20 +270,23 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
             } else {
                 pixel = false;
                 // main_raytracing.cu:195-199
-                const float fs = (float)a.spp;
+                const float fs = (float)A(&RenderArgs::spp);
                 // the reference's alpha sum adds 1.0f per sample: (float)sample exactly, and stuck at 2^24
                 // from there on (2^24 + 1 rounds back to 2^24 in fp32)
                 const rtm::f4 res{acc_r / fs, acc_g / fs, acc_b / fs, (float)min(sample, 1 << 24) / fs};
-                const float lerp = a.frame_index > 0 ? 1.0f / (float)(a.frame_index + 1) : 1.0f;
+                const int frame_index = A(&RenderArgs::frame_index);
+                const float lerp = frame_index > 0 ? 1.0f / (float)(frame_index + 1) : 1.0f;
                 float4 prev;
                 float4* out;
-                if (a.out_shard) {
-                    prev = a.last ? reinterpret_cast<const float4*>(a.last)[slot] : make_float4(0, 0, 0, 0);
-                    out = a.out_shard + slot;
+                float4* const out_shard = A(&RenderArgs::out_shard);
+                const char* const last = A(&RenderArgs::last);
+                if (out_shard) {
+                    prev = last ? reinterpret_cast<const float4*>(last)[slot] : make_float4(0, 0, 0, 0);
+                    out = out_shard + slot;
                 } else {
-                    prev = a.last ? *reinterpret_cast<const float4*>(a.last + (size_t)y * a.pitch + (size_t)x * 16)
-                                  : make_float4(0, 0, 0, 0);
-                    out = reinterpret_cast<float4*>(a.surface + (size_t)y * a.pitch + (size_t)x * 16);
+                    const size_t at = (size_t)y * A(&RenderArgs::pitch) + (size_t)x * 16;
+                    prev = last ? *reinterpret_cast<const float4*>(last + at) : make_float4(0, 0, 0, 0);
+                    out = reinterpret_cast<float4*>(A(&RenderArgs::surface) + at);
                 }
                 const rtm::f4 o = rtm::mix4(rtm::f4{prev.x, prev.y, prev.z, prev.w}, res, lerp);
                 *out = make_float4(o.x, o.y, o.z, 1.0f);
@@ -259,7 +298,10 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
                 rs->v[3] = rng.v3;
                 rs->v[4] = rng.v4;
                 // per-pixel work for rt_lane_plan: traversal steps + 3 per big leaf + 1 per segment
-                if ((MODE & 8) && a.lane_cost) a.lane_cost[slot] = c.lane_work + (uint32_t)c.seg;
+                if (MODE & 8) {
+                    uint32_t* const lane_cost = A(&RenderArgs::lane_cost);
+                    if (lane_cost) lane_cost[slot] = c.lane_work + (uint32_t)c.seg;
+                }
             }
         }
 #ifdef RT_LIVE_HIST  // diagnostic build (tools/lane_hist.sh LIVE=1): segment-loop wave cycles by live pixels
@@ -292,8 +334,10 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
         const rtm::f3 nd = rtm::normalize(rd);
         if (path) {
             c.seg++;
-            for (int i = 0; i < a.sphere_count; i++) {
-                const GeometrySphere& sp = a.spheres[i];
+            const int sphere_count = A(&RenderArgs::sphere_count);
+            const GeometrySphere* const spheres = A(&RenderArgs::spheres);
+            for (int i = 0; i < sphere_count; i++) {
+                const GeometrySphere& sp = spheres[i];
                 float dist;
                 if (rtd::intersect_sphere(ro, nd, ld3(sp.position), sp.radius * sp.radius, &dist)) {
                     if (dist >= h.best) continue;
@@ -304,13 +348,13 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
                 }
             }
         }
-        rtfast::Ray R = rtfast::make_ray(ro, rd, nd, scene_fast);
+        rtfast::Ray R = rtfast::make_ray(ro, rd, nd, A(&RenderArgs::scene_fast) != 0);
         rtfast::trace<STATS, MODE>(nodes4, tris, a.pairs, a.tree, a.ltris, a.flat, a.spairs, a.tune, stk, scratch, R, h,
-                                   path, c, a.quads, a.units, a.face_leaf, mail);
+                                   path, c, a.quads, a.units, a.face_leaf);
         if (!path) continue;
 
-        bool end = shade_segment<STATS>(a, h, ro, rd, nd, rng, color, thr, c);
-        if (++bounce >= a.bounces) end = true;
+        bool end = shade_segment<STATS, COLD>(a, h, ro, rd, nd, rng, color, thr, c);
+        if (++bounce >= A(&RenderArgs::bounces)) end = true;
         if (end) {
             acc_r += color.x;
             acc_g += color.y;
@@ -320,13 +364,15 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
         }
     }
 
-    if (a.seg_counter) {
+    if (unsigned long long* const seg_counter = A(&RenderArgs::seg_counter)) {
         unsigned long long v = c.seg;
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        if ((threadIdx.x & 63) == 0) atomicAdd(a.seg_counter, v);
+        if ((threadIdx.x & 63) == 0) atomicAdd(seg_counter, v);
     }
     // per-wave cost for cost-aware shard plans (rt_render_params.wave_clock; one store per wave)
-    if (a.wave_clock && lane == 0) a.wave_clock[lb] = __builtin_amdgcn_s_memrealtime() - rt_start;
+    unsigned long long* const wave_clock = A(&RenderArgs::wave_clock);
+    if (wave_clock && lane == 0) wave_clock[lb] = __builtin_amdgcn_s_memrealtime() - rt_start;
+    unsigned long long* const stats = A(&RenderArgs::stats);
     unsigned long long lane_max = c.l_small;  // the busiest lane's small steps (timing frame)
     if (MODE & 8)
         for (int off = 32; off > 0; off >>= 1) {
@@ -335,37 +381,37 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
         }
     unsigned long long lane_sum = c.l_small;  // the wave's lane-steps in small-step iterations (timing frame)
     unsigned long long big_sum[5] = {c.big_tests, c.tw_dec, c.tw_test, c.end2, c.redo};  // per lane -> the wave's
-    if ((MODE & 8) && a.stats)
+    if ((MODE & 8) && stats)
         for (int off = 32; off > 0; off >>= 1) {
             lane_sum += __shfl_xor(lane_sum, off);
             for (int k = 0; k < 5; k++) big_sum[k] += __shfl_xor(big_sum[k], off);
         }
-    if ((MODE & 8) && a.stats && lane == 0) {  // timing frame: per-wave phase clocks
-        atomicAdd(a.stats + RT_STAT_CYCLES_SMALL, c.cy_small);
-        atomicAdd(a.stats + RT_STAT_CYCLES_BIG, c.cy_big);
-        atomicAdd(a.stats + RT_STAT_CYCLES_TOTAL, __builtin_amdgcn_s_memtime() - t_start);
-        atomicAdd(a.stats + RT_STAT_ROUNDS_COOP, c.r_coop);
-        atomicAdd(a.stats + RT_STAT_ROUNDS_SHARED, c.r_shared);
-        atomicAdd(a.stats + RT_STAT_COOP_RAYS, c.coop_rays);
-        atomicAdd(a.stats + RT_STAT_WAVE_SMALL_ITERS, c.w_small);  // small-step wave iterations
-        atomicAdd(a.stats + RT_STAT_LANE_SMALL, lane_sum);          // lane-steps in them
-        atomicAdd(a.stats + RT_STAT_BIG_TESTS, big_sum[0]);
-        atomicAdd(a.stats + RT_STAT_TWIN_DECIDED, big_sum[1]);
-        atomicAdd(a.stats + RT_STAT_TWIN_TESTS, big_sum[2]);
-        atomicAdd(a.stats + RT_STAT_WAVE_BIG_ITERS, c.big_iters);
-        atomicAdd(a.stats + RT_STAT_DEFER_END2, big_sum[3]);
-        atomicAdd(a.stats + RT_STAT_DEFER_REDO, big_sum[4]);
+    if ((MODE & 8) && stats && lane == 0) {  // timing frame: per-wave phase clocks
+        atomicAdd(stats + RT_STAT_CYCLES_SMALL, c.cy_small);
+        atomicAdd(stats + RT_STAT_CYCLES_BIG, c.cy_big);
+        atomicAdd(stats + RT_STAT_CYCLES_TOTAL, __builtin_amdgcn_s_memtime() - t_start);
+        atomicAdd(stats + RT_STAT_ROUNDS_COOP, c.r_coop);
+        atomicAdd(stats + RT_STAT_ROUNDS_SHARED, c.r_shared);
+        atomicAdd(stats + RT_STAT_COOP_RAYS, c.coop_rays);
+        atomicAdd(stats + RT_STAT_WAVE_SMALL_ITERS, c.w_small);  // small-step wave iterations
+        atomicAdd(stats + RT_STAT_LANE_SMALL, lane_sum);          // lane-steps in them
+        atomicAdd(stats + RT_STAT_BIG_TESTS, big_sum[0]);
+        atomicAdd(stats + RT_STAT_TWIN_DECIDED, big_sum[1]);
+        atomicAdd(stats + RT_STAT_TWIN_TESTS, big_sum[2]);
+        atomicAdd(stats + RT_STAT_WAVE_BIG_ITERS, c.big_iters);
+        atomicAdd(stats + RT_STAT_DEFER_END2, big_sum[3]);
+        atomicAdd(stats + RT_STAT_DEFER_REDO, big_sum[4]);
         // cooperative leaf-tree walk (wave-level): rays, subtree + cluster tests, triangle rounds
-        atomicAdd(a.stats + RT_STAT_TREE_NODES, c.ktest);
-        atomicAdd(a.stats + RT_STAT_TREE_TRI_TESTS, c.ktri);
-        atomicAdd(a.stats + RT_STAT_WAVE_BIG_TRIS, c.w_big);
-        atomicAdd(a.stats + RT_STAT_LANE_BIG_TRIS, c.l_big);
-        atomicAdd(a.stats + RT_STAT_CYCLES_TREE_CLUSTERS, c.cy_tcl);
-        atomicAdd(a.stats + RT_STAT_CYCLES_TREE_CUT, c.cy_tree);
-        atomicAdd(a.stats + RT_STAT_CYCLES_TREE_TRIS, c.cy_ttri);
+        atomicAdd(stats + RT_STAT_TREE_NODES, c.ktest);
+        atomicAdd(stats + RT_STAT_TREE_TRI_TESTS, c.ktri);
+        atomicAdd(stats + RT_STAT_WAVE_BIG_TRIS, c.w_big);
+        atomicAdd(stats + RT_STAT_LANE_BIG_TRIS, c.l_big);
+        atomicAdd(stats + RT_STAT_CYCLES_TREE_CLUSTERS, c.cy_tcl);
+        atomicAdd(stats + RT_STAT_CYCLES_TREE_CUT, c.cy_tree);
+        atomicAdd(stats + RT_STAT_CYCLES_TREE_TRIS, c.cy_ttri);
         // RT_TUNE bit 11: per-wave clocks (start, end) after the counters, for load-balance analysis
-        if (a.tune & 2048u) {
-            unsigned long long* w = a.stats + RT_STAT_COUNT + 8 * (size_t)lb;
+        if (wave_times) {
+            unsigned long long* w = stats + RT_STAT_COUNT + 8 * (size_t)lb;
             w[0] = rt_start;  // 100 MHz device clock (one time base across waves)
             w[1] = __builtin_amdgcn_s_memrealtime();
             w[2] = c.cy_small;
@@ -377,75 +423,61 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
         }
     }
     if (STATS) {
-        atomicAdd(a.stats + RT_STAT_SEGMENTS, c.seg);
-        atomicAdd(a.stats + RT_STAT_NODES, c.node);
-        atomicAdd(a.stats + RT_STAT_TRI_TESTS, c.tri);
-        atomicAdd(a.stats + RT_STAT_TRI_ACCEPTS, c.tacc);
-        atomicAdd(a.stats + RT_STAT_SPHERE_ACCEPTS, c.sacc);
-        atomicAdd(a.stats + RT_STAT_HITS, c.hit);
-        atomicAdd(a.stats + RT_STAT_MISSES, c.miss);
-        atomicAdd(a.stats + RT_STAT_WAVE_SMALL_ITERS, c.w_small);
-        atomicAdd(a.stats + RT_STAT_LANE_SMALL, c.l_small);
-        atomicAdd(a.stats + RT_STAT_WAVE_BIG_TRIS, c.w_big);
-        atomicAdd(a.stats + RT_STAT_LANE_BIG_TRIS, c.l_big);
-        atomicAdd(a.stats + RT_STAT_CYCLES_TREE_CLUSTERS, c.cy_tcl);
-        atomicAdd(a.stats + RT_STAT_CYCLES_TREE_CUT, c.cy_tree);
-        atomicAdd(a.stats + RT_STAT_CYCLES_TREE_TRIS, c.cy_ttri);
-        atomicAdd(a.stats + RT_STAT_WAVE_SEGMENT_ITERS, c.w_seg);
-        atomicAdd(a.stats + RT_STAT_LANE_SEGMENTS, c.l_seg);
-        atomicAdd(a.stats + RT_STAT_TREE_NODES, c.ktest);
-        atomicAdd(a.stats + RT_STAT_TREE_TRI_TESTS, c.ktri);
+        atomicAdd(stats + RT_STAT_SEGMENTS, c.seg);
+        atomicAdd(stats + RT_STAT_NODES, c.node);
+        atomicAdd(stats + RT_STAT_TRI_TESTS, c.tri);
+        atomicAdd(stats + RT_STAT_TRI_ACCEPTS, c.tacc);
+        atomicAdd(stats + RT_STAT_SPHERE_ACCEPTS, c.sacc);
+        atomicAdd(stats + RT_STAT_HITS, c.hit);
+        atomicAdd(stats + RT_STAT_MISSES, c.miss);
+        atomicAdd(stats + RT_STAT_WAVE_SMALL_ITERS, c.w_small);
+        atomicAdd(stats + RT_STAT_LANE_SMALL, c.l_small);
+        atomicAdd(stats + RT_STAT_WAVE_BIG_TRIS, c.w_big);
+        atomicAdd(stats + RT_STAT_LANE_BIG_TRIS, c.l_big);
+        atomicAdd(stats + RT_STAT_CYCLES_TREE_CLUSTERS, c.cy_tcl);
+        atomicAdd(stats + RT_STAT_CYCLES_TREE_CUT, c.cy_tree);
+        atomicAdd(stats + RT_STAT_CYCLES_TREE_TRIS, c.cy_ttri);
+        atomicAdd(stats + RT_STAT_WAVE_SEGMENT_ITERS, c.w_seg);
+        atomicAdd(stats + RT_STAT_LANE_SEGMENTS, c.l_seg);
+        atomicAdd(stats + RT_STAT_TREE_NODES, c.ktest);
+        atomicAdd(stats + RT_STAT_TREE_TRI_TESTS, c.ktri);
     }
 }
 
 // The production kernel.  The _w5 / _w6 / _w7 variants ask the compiler for 5 / 6 / 7 waves per
 // SIMD (fewer registers, more spilled) -- an occupancy / spill trade-off (RT_TUNE bits 9-10:
 // 0 = _w5, the default; 1 = unconstrained; 2 = _w6; 3 = _w7).
-#if defined(RT_PAIR)  // the pair's mailbox (rt_fast.h), cleared before either wave can use it
-#define RT_PAIR_MAIL                                                \
-    __shared__ uint32_t pair_mail[rtfast::PAIR_MAIL_WORDS];        \
-    if (threadIdx.x == 0) pair_mail[0] = 0u;                        \
-    __syncthreads();
-#define RT_PAIR_MAIL_ARG pair_mail
-#else
-#define RT_PAIR_MAIL
-#define RT_PAIR_MAIL_ARG nullptr
-#endif
 template <int STACK, bool STATS, int MODE>
-__global__ __launch_bounds__(WGL) void render_fast_kernel(RenderArgs a) {
+__global__ __launch_bounds__(WAVE) void render_fast_kernel(RenderArgs a) {
     constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL;  // LDS entries; deeper ones in `ovf` (rt_fast.h Stack)
-    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WGL];  // one word per entry (rt_fast.h pop)
+    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE];  // one word per entry (rt_fast.h pop)
     __shared__ uint32_t scratch_lds[((MODE & 4) ? 64 : 0) + rtfast::DEFER_WORDS];  // coop_tree's compaction, deferred leaves
     uint32_t ovf[STACK > SL ? STACK - SL : 1];
-    RT_PAIR_MAIL
-    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL, WGL>{stack_lds, ovf}, scratch_lds, RT_PAIR_MAIL_ARG);
+    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds);
 }
 template <int STACK, bool STATS, int MODE>
-__global__ __launch_bounds__(WGL) __attribute__((amdgpu_waves_per_eu(5))) void render_fast_kernel_w5(RenderArgs a) {
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(5))) void render_fast_kernel_w5(RenderArgs a) {
     constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL;  // LDS entries; deeper ones in `ovf` (rt_fast.h Stack)
-    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WGL];  // one word per entry (rt_fast.h pop)
+    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE];  // one word per entry (rt_fast.h pop)
     __shared__ uint32_t scratch_lds[((MODE & 4) ? 64 : 0) + rtfast::DEFER_WORDS];  // coop_tree's compaction, deferred leaves
     uint32_t ovf[STACK > SL ? STACK - SL : 1];
-    RT_PAIR_MAIL
-    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL, WGL>{stack_lds, ovf}, scratch_lds, RT_PAIR_MAIL_ARG);
+    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds);
 }
 template <int STACK, bool STATS, int MODE>
-__global__ __launch_bounds__(WGL) __attribute__((amdgpu_waves_per_eu(6))) void render_fast_kernel_w6(RenderArgs a) {
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(6))) void render_fast_kernel_w6(RenderArgs a) {
     constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL;  // LDS entries; deeper ones in `ovf` (rt_fast.h Stack)
-    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WGL];  // one word per entry (rt_fast.h pop)
+    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE];  // one word per entry (rt_fast.h pop)
     __shared__ uint32_t scratch_lds[((MODE & 4) ? 64 : 0) + rtfast::DEFER_WORDS];  // coop_tree's compaction, deferred leaves
     uint32_t ovf[STACK > SL ? STACK - SL : 1];
-    RT_PAIR_MAIL
-    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL, WGL>{stack_lds, ovf}, scratch_lds, RT_PAIR_MAIL_ARG);
+    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds);
 }
 template <int STACK, bool STATS, int MODE>
-__global__ __launch_bounds__(WGL) __attribute__((amdgpu_waves_per_eu(7))) void render_fast_kernel_w7(RenderArgs a) {
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7))) void render_fast_kernel_w7(RenderArgs a) {
     constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL;  // LDS entries; deeper ones in `ovf` (rt_fast.h Stack)
-    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WGL];  // one word per entry (rt_fast.h pop)
+    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE];  // one word per entry (rt_fast.h pop)
     __shared__ uint32_t scratch_lds[((MODE & 4) ? 64 : 0) + rtfast::DEFER_WORDS];  // coop_tree's compaction, deferred leaves
     uint32_t ovf[STACK > SL ? STACK - SL : 1];
-    RT_PAIR_MAIL
-    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL, WGL>{stack_lds, ovf}, scratch_lds, RT_PAIR_MAIL_ARG);
+    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds);
 }
 
 // Waves of `kernel` the device holds at once (refill launches size their grid to it).
@@ -494,7 +526,7 @@ hipError_t launch_grid(K kernel, const RenderArgs& args, int waves, bool refill,
             res = std::min(res, cap * 4 * cus);  // the residency cap holds fewer
         if (res > 0) grid = std::min(waves, res);
     }
-    hipLaunchKernelGGL(kernel, dim3((grid + WG_WAVES - 1) / WG_WAVES), dim3(WGL), lds, stream, args);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE), lds, stream, args);
     return hipGetLastError();
 }
 

@@ -229,6 +229,27 @@ bool needs_experimental(const rt_render_params* p, bool has_tree, bool screens) 
     return (p->tune & 4096u) != 0 || (!has_tree && (mode == 2u || mode == 3u));
 }
 
+// RT_TUNE bits a render kernel itself reads (rt_fast.h trace / big_round / coop_tree: bits 0, 13-15, 21-24, 26,
+// 30, 31; rt_fast_body.h: the XCD run length 16-19, the per-wave clock records 11).  The others choose a
+// kernel or drop a mirror array on the host.
+constexpr uint32_t kKernelTuneBits = 1u | (1u << 11) | (7u << 13) | (15u << 16) | (7u << 21) | (1u << 24) | (1u << 26) |
+                                     (1u << 30) | (1u << 31);
+
+// MODE 17 (or its timing variant 25) with the lean bit (rt_fast.h LEAN_BIT) when the frame sets no knob the
+// kernel reads and the scene's mirror holds every array that variant assumes; `mode` itself otherwise, and for
+// the leaf-tree modes 21 / 29, which have no lean variant (rt_fast_lean.hip: measured slower).
+int lean_mode(const RenderArgs& a, int mode) {
+    if ((mode & 4) || (a.tune & kKernelTuneBits)) return mode;
+    const bool have = a.nodes && a.tris && a.spairs && a.pairs && a.quads && a.units;
+    return have ? mode | rtfast::LEAN_BIT : mode;
+}
+
+// The production variant `mode` (17 / 21): the lean kernel when lean_mode allows it, else the general one.
+hipError_t launch_prod(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s) {
+    const int m = lean_mode(a, mode);
+    return (m & rtfast::LEAN_BIT) ? launch_fast_lean(stack, m, a, waves, s) : launch_fast_prod(stack, m, a, waves, s);
+}
+
 hipError_t launch_fast(const RenderArgs& args, int waves, int depth, bool stats, hipStream_t s) {
     const int stack = (depth >= 0 && depth + 2 <= 30) ? 30 : (depth >= 0 && depth + 2 <= 40) ? 40 : 64;
     // statistics: the reference's work on scalar records (RT_TUNE bit 7: through the leaf trees);
@@ -238,12 +259,13 @@ hipError_t launch_fast(const RenderArgs& args, int waves, int depth, bool stats,
     const bool scr = args.screens != 0 && (args.tune & 4096u) == 0;
     if (stats && (args.tune & 256u)) {
         if (scr) return x ? x->fast_screen(stack, args.tree ? 61 : 57, args, waves, s) : hipErrorNotSupported;
-        return launch_fast_timing(stack, args.tree ? 29 : (args.tune & 4096u) ? 9 : 25, args, waves, s);
+        if (!args.tree && (args.tune & 4096u)) return launch_fast_timing(stack, 9, args, waves, s);
+        return launch_fast_timing(stack, lean_mode(args, args.tree ? 29 : 25), args, waves, s);
     }
     // per-pixel work (rt_render_params.lane_cost): the timing variant of the production kernel
     if (!stats && args.lane_cost) {
         if (scr) return x ? x->fast_screen(stack, args.tree ? 61 : 57, args, waves, s) : hipErrorNotSupported;
-        return launch_fast_timing(stack, args.tree ? 29 : 25, args, waves, s);
+        return launch_fast_timing(stack, lean_mode(args, args.tree ? 29 : 25), args, waves, s);
     }
     if (stats) return launch_fast_stats(stack, (args.tree && (args.tune & 128u)) ? 6 : 2, args, waves, s);
     // MODE bit 4: inner-node and small-leaf steps in separate iterations (rt_fast.h trace); RT_TUNE
@@ -255,11 +277,11 @@ hipError_t launch_fast(const RenderArgs& args, int waves, int depth, bool stats,
     if (scr && split && (args.tree || ((args.tune >> 4) & 3u) < 2u))
         return x ? x->fast_screen(stack, args.tree ? 53 : 49, args, waves, s) : hipErrorNotSupported;
     if (args.tree) {
-        if (split) return launch_fast_prod(stack, 21, args, waves, s);
+        if (split) return launch_prod(stack, 21, args, waves, s);
         return x ? x->fast_ab(stack, 5, args, waves, s) : hipErrorNotSupported;
     }
     const uint32_t mode = (args.tune >> 4) & 3u;
-    if (split && mode < 2) return launch_fast_prod(stack, 17, args, waves, s);
+    if (split && mode < 2) return launch_prod(stack, 17, args, waves, s);
     if (!x) return hipErrorNotSupported;
     if (mode == 2) return x->fast_ab(stack, 2, args, waves, s);
     if (mode == 3) return x->fast_ab(stack, 0, args, waves, s);

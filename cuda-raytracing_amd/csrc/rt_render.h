@@ -12,7 +12,8 @@ namespace rtk {
 
 // In librt_hip.so (the product): the kernels the production path launches.
 hipError_t launch_fast_prod(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);    // 17, 21
-hipError_t launch_fast_timing(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);  // 25, 29, 9
+hipError_t launch_fast_lean(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);    // 17 | 128
+hipError_t launch_fast_timing(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);  // 25, 29, 9, 25 | 128
 hipError_t launch_fast_stats(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);   // 2, 6 (counting)
 // The reference-layout tracer (flat = false) or the exact-division flat tracer (rt_ref.hip).
 hipError_t launch_ref_tracer(bool flat, const RenderArgs& a, int waves, int depth, bool stats, hipStream_t s);
