@@ -82,7 +82,29 @@ class RenderParams(ctypes.Structure):
                 ("waves_per_simd", ctypes.c_int32), ("lone_slots", ctypes.c_void_p), ("lone_count", ctypes.c_int64)]
 
 
+class Ray(ctypes.Structure):
+    """rt_ray (rt_abi.h): one row of a float32 [N, 8] ray tensor."""
+    _fields_ = [("origin", ctypes.c_float * 3), ("tmax", ctypes.c_float), ("direction", ctypes.c_float * 3),
+                ("reserved", ctypes.c_uint32)]
+
+
+class Hit(ctypes.Structure):
+    """rt_hit (rt_abi.h): one row of a float32 [N, 12] hit tensor (hit_fields gives typed views)."""
+    _fields_ = [("t", ctypes.c_float), ("kind", ctypes.c_uint32), ("id", ctypes.c_uint32), ("material", ctypes.c_uint32),
+                ("normal", ctypes.c_float * 3), ("bx", ctypes.c_float), ("position", ctypes.c_float * 3),
+                ("by", ctypes.c_float)]
+
+
+class TraceParams(ctypes.Structure):
+    _fields_ = [("rays", ctypes.c_void_p), ("count", ctypes.c_int64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("hits", ctypes.c_void_p), ("flags", ctypes.c_uint32), ("waves_per_simd", ctypes.c_int32)]
+
+
+HIT_MISS, HIT_SPHERE, HIT_TRIANGLE = 0, 1, 2  # rt_hit.kind
+RAY_TMAX = 1e30  # the renderer's own initial closest distance (main_raytracing.cu:85)
+
 assert ctypes.sizeof(GPUScene) == 136 and ctypes.sizeof(GPUMaterial) == 64
+assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(Hit) == 48 and ctypes.sizeof(TraceParams) == 40
 
 # name -> (restype, argtypes); every symbol include/rt_abi.h declares.
 _P, _I, _U32, _U64, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_size_t
@@ -91,6 +113,7 @@ SIGNATURES = {
     "raytracing_process": (None, [_P, _P, _I, _I, _SZ, _I, _P]),
     "init_rng": (None, [_U32, _U32, _P, ctypes.c_uint]),
     "rt_render": (_I, [ctypes.POINTER(RenderParams), _P, _P]),
+    "rt_trace_rays": (_I, [ctypes.POINTER(TraceParams), _P, _P]),
     "rt_foreign_mirror_wait": (_I, [_P]),
     "rt_foreign_last_tracer": (_I, [_P]),
     "rt_experimental_loaded": (_I, []),
@@ -153,6 +176,7 @@ SIGNATURES = {
     "rt_scene_host_arrays": (_SZ, [_P, ctypes.POINTER(_P), ctypes.POINTER(_SZ), ctypes.POINTER(_P),
                                    ctypes.POINTER(_SZ), ctypes.POINTER(_P), ctypes.POINTER(_SZ), ctypes.POINTER(_P)]),
     "rt_scene_bvh_max_depth": (_I, [_P]),
+    "rt_scene_materials": (_I, [_P, _P, ctypes.POINTER(_SZ)]),
     "rt_bvh_build_device": (_I, [_P, _U32, _P, _U32, _P, _P, ctypes.POINTER(_U32), ctypes.POINTER(_I), _P]),
     "rt_scene_mirror_info": (_I, [_P, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
     "rt_scene_mirror_copy": (_I, [_P, _P, _P, _P]),
@@ -350,6 +374,16 @@ class Scene:
                "rt_scene_mirror_twins")
         return q, u
 
+    def materials(self):
+        """Host copy of the GPUMaterial array as (M, 16) float32: albedo 0-3, emissive 4-7, specular 8-11,
+        roughness, specular_percent, IOR, padding (what rt_hit.material indexes)."""
+        n = ctypes.c_size_t()
+        _check(lib().rt_scene_materials(self.handle, None, ctypes.byref(n)), "rt_scene_materials")
+        out = np.zeros((n.value, 16), dtype=np.float32)
+        if n.value:
+            _check(lib().rt_scene_materials(self.handle, out.ctypes.data, ctypes.byref(n)), "rt_scene_materials")
+        return out
+
     def host_arrays(self):
         """numpy copies of the host arrays: nodes (N,8) f32/u32 view, face indices, vertices, faces."""
         import numpy as np
@@ -468,6 +502,63 @@ def render(scene, surface, last, width, height, spp, bounces, frame_index=0, sha
         p.stats = stats.data_ptr()
     gpu = scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene)  # Scene, or a GPUScene filled by the caller
     _check(lib().rt_render(ctypes.byref(p), ctypes.cast(gpu, ctypes.c_void_p), _stream_ptr(stream)), "rt_render")
+
+
+def _trace(scene, rays, count, width, height, hits, stream, waves_per_simd):
+    if hits is None:
+        hits = torch.empty((count, 12), dtype=torch.float32, device=rays.device if rays is not None else "cuda")
+    assert hits.dtype == torch.float32 and hits.is_cuda and hits.is_contiguous() and hits.dim() == 2
+    assert hits.shape[1] == 12 and hits.shape[0] >= count
+    p = TraceParams()
+    p.rays = rays.data_ptr() if rays is not None else None
+    p.count, p.width, p.height = count, width, height
+    p.hits = hits.data_ptr()
+    p.waves_per_simd = int(waves_per_simd)
+    gpu = scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene)
+    _check(lib().rt_trace_rays(ctypes.byref(p), ctypes.cast(gpu, ctypes.c_void_p), _stream_ptr(stream)), "rt_trace_rays")
+    return hits
+
+
+def trace_rays(scene, rays, hits=None, stream=None, waves_per_simd=0):
+    """rt_trace_rays: the closest hit of every ray of a float32 CUDA tensor [N, 8] (rt_ray rows: origin,
+    tmax, direction, a zero word) on `stream` (default: torch's current stream), as a float32 [N, 12]
+    tensor of rt_hit rows (`hits`, or a new one; hit_fields gives typed views).  The scene must have
+    been uploaded (Scene.upload; its RNG pointer may be 0 for a scene that is only queried)."""
+    assert rays.dtype == torch.float32 and rays.is_cuda and rays.is_contiguous() and rays.dim() == 2 and rays.shape[1] == 8
+    return _trace(scene, rays, rays.shape[0], 0, 0, hits, stream, waves_per_simd)
+
+
+def trace_camera(scene, width, height, hits=None, stream=None, waves_per_simd=0):
+    """rt_trace_rays in camera mode: the rays through the pixel centres of the uploaded scene's camera
+    (Scene.set_viewport before upload), row i = pixel (i % width, i // width); float32 [H*W, 12]."""
+    return _trace(scene, None, int(width) * int(height), int(width), int(height), hits, stream, waves_per_simd)
+
+
+def hit_fields(hits):
+    """Typed views of a [N, 12] hit tensor (torch or numpy): t, kind / id / material (int32), normal [N, 3],
+    position [N, 3], bx, by."""
+    ints = hits.view(torch.int32) if isinstance(hits, torch.Tensor) else hits.view(np.int32)
+    return {"t": hits[:, 0], "kind": ints[:, 1], "id": ints[:, 2], "material": ints[:, 3], "normal": hits[:, 4:7],
+            "bx": hits[:, 7], "position": hits[:, 8:11], "by": hits[:, 11]}
+
+
+def gbuffer(scene, width, height, stream=None, waves_per_simd=0):
+    """First-hit images of an uploaded Scene's camera (rt_trace_rays in camera mode: the pixel centres, no
+    jitter) as device tensors, rows bottom to top like the surface: depth [H, W] (t; inf on a miss),
+    normal / position / albedo [H, W, 3] (0 on a miss; albedo is the hit material's), material, prim (-1 on
+    a miss; sphere or face index) and kind [H, W] int32."""
+    w, h = int(width), int(height)
+    f = hit_fields(trace_camera(scene, w, h, stream=stream, waves_per_simd=waves_per_simd))
+    hit = f["kind"] != HIT_MISS
+    mats = torch.from_numpy(scene.materials()).to(hit.device)
+    albedo = torch.zeros((w * h, 3), dtype=torch.float32, device=hit.device)
+    if mats.shape[0]:
+        albedo = torch.where(hit[:, None], mats[f["material"].long().clamp(0, mats.shape[0] - 1), :3], albedo)
+    return {"depth": torch.where(hit, f["t"], torch.full_like(f["t"], float("inf"))).reshape(h, w),
+            "normal": f["normal"].reshape(h, w, 3).clone(), "position": f["position"].reshape(h, w, 3).clone(),
+            "albedo": albedo.reshape(h, w, 3), "material": f["material"].reshape(h, w).clone(),
+            "prim": torch.where(hit, f["id"], torch.full_like(f["id"], -1)).reshape(h, w),
+            "kind": f["kind"].reshape(h, w).clone()}
 
 
 def foreign_mirror_wait(gpu_scene):
@@ -694,6 +785,13 @@ class RayTracer:
         self.last_frame.copy_(self.surface)
         self.frame_index += 1
         return surface_view(self.surface, self.width)
+
+    def gbuffer(self, stream=None, waves_per_simd=0):
+        """First-hit images of the current camera and size (module-level gbuffer()).  Uploads the scene
+        like process(); the frame index, the surfaces and the RNG states are left alone."""
+        self.scene.set_viewport(self.width, self.height)
+        self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
+        return gbuffer(self.scene, self.width, self.height, stream=stream, waves_per_simd=waves_per_simd)
 
     def save(self, path):
         """The current frame: ``.pfm`` linear RGB, ``.ppm`` as the reference's viewer shows it

@@ -898,6 +898,62 @@ extern "C" int rt_render(const rt_render_params* p, const GPUScene* scene, void*
     return check(e, "render_kernel launch");
 }
 
+// Ray queries (rt_abi.h): argument checks, then the query kernel (rt_query.hip) in the variant a production
+// frame of this scene runs at RT_TUNE 0 -- the choices of launch_fast and lean_mode.  Stream-ordered: no
+// synchronisation, no allocation.
+extern "C" int rt_trace_rays(const rt_trace_params* p, const GPUScene* scene, void* stream) {
+    if (!p) return set_error("rt_trace_rays: null params");
+    if (!scene) return set_error("rt_trace_rays: null scene");
+    if (!p->hits) return set_error("rt_trace_rays: null hits");
+    if (p->flags != 0) return set_error("rt_trace_rays: flags must be 0");
+    if (p->waves_per_simd != 0 && (p->waves_per_simd < 5 || p->waves_per_simd > 7))
+        return set_error("rt_trace_rays: waves_per_simd must be 0 (default), 5, 6 or 7");
+    const bool camera = p->rays == nullptr;
+    if (camera && (p->width <= 0 || p->height <= 0)) return set_error("rt_trace_rays: camera mode needs width, height > 0");
+    const int64_t count = camera ? (int64_t)p->width * p->height : p->count;
+    if (count < 0) return set_error("rt_trace_rays: negative count");
+    if (count > (int64_t)1 << 31) return set_error("rt_trace_rays: more than 2^31 rays in one call");
+    if ((((uintptr_t)p->rays) | ((uintptr_t)p->hits)) & 15u) return set_error("rt_trace_rays: rays and hits must be 16-byte aligned");
+    if (count == 0) return 0;
+
+    MirrorDevice mir;
+    if (!rt_internal_lookup_mirror(scene, &mir) || !mir.owned)
+        return set_error("rt_trace_rays: this GPUScene was not uploaded by rt_scene_upload (a foreign scene has no private "
+                         "mirror to query; foreign scenes are not supported here)");
+    if (!mir.nodes || !mir.tris) return set_error("rt_trace_rays: the scene's mirror has no triangles to traverse");
+    if (scene->sphere_count > 0 && !scene->gpu_spheres) return set_error("rt_trace_rays: sphere_count without spheres");
+    // a short buffer would fault the GPU
+    if (!camera && bytes_from(p->rays) < (size_t)count * sizeof(rt_ray)) return set_error("rt_trace_rays: rays too small");
+    if (bytes_from(p->hits) < (size_t)count * sizeof(rt_hit)) return set_error("rt_trace_rays: hits too small");
+
+    QueryArgs q;
+    std::memset(&q, 0, sizeof(q));
+    q.rays = p->rays;
+    q.hits = p->hits;
+    q.count = count;
+    q.width = camera ? p->width : 1, q.height = camera ? p->height : 1;
+    q.cam = scene->camera;
+    q.spheres = scene->gpu_spheres;
+    q.sphere_count = scene->sphere_count;
+    q.scene_fast = mir.fast ? 1 : 0;
+    q.faces = scene->gpu_faces;
+    q.vertices = scene->gpu_vertices;
+    q.nodes = (const GPUBVHNode*)mir.nodes;
+    q.tris = (const FlatTri*)mir.tris;
+    q.pairs = (const float4*)mir.pairs, q.quads = (const float4*)mir.quads, q.units = (const float4*)mir.units;
+    q.tree = (const float4*)mir.tree, q.ltris = (const float4*)mir.ltris, q.spairs = (const float4*)mir.spairs;
+    q.flat = (const float4*)mir.flat;
+    q.face_leaf = (const uint32_t*)mir.face_leaf;
+    const int depth = mir.depth;
+    const int stack = (depth >= 0 && depth + 2 <= 30) ? 30 : (depth >= 0 && depth + 2 <= 40) ? 40 : 64;
+    int mode = q.tree ? 21 : 17;
+    if (mode == 17 && q.spairs && q.pairs && q.quads && q.units) mode |= rtfast::LEAN_BIT;  // lean_mode's conditions
+    // default occupancy, measured (profiles/query_timing.txt): MODE 17 fits 7 waves per SIMD with 2 spilled
+    // registers (incoherent rays 1.20 vs 1.35 ms at 5); the leaf-tree MODE 21 spills ~100 there (5.0 vs 3.9 ms)
+    const int w = p->waves_per_simd ? p->waves_per_simd : (mode == 21 ? 5 : 7);
+    return check(launch_query(stack, mode, w, q, (hipStream_t)stream), "query_kernel launch");
+}
+
 // 1 when librt_hip_exp.so's render paths are registered (rt_render.h ExperimentalKernels).
 extern "C" int rt_experimental_loaded() { return rtk::experimental_kernels() ? 1 : 0; }
 

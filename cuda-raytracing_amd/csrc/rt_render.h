@@ -18,6 +18,28 @@ hipError_t launch_fast_stats(int stack, int mode, const RenderArgs& a, int waves
 // The reference-layout tracer (flat = false) or the exact-division flat tracer (rt_ref.hip).
 hipError_t launch_ref_tracer(bool flat, const RenderArgs& a, int waves, int depth, bool stats, hipStream_t s);
 
+// The ray-query kernel (rt_query.hip, rt_trace_rays): one ray per lane through rtfast::trace, no shading.
+// `rays` null = camera mode (pixel centres of `cam`, width x height).  The mirror arrays are the ones a
+// render launch passes to trace (rt_kernel.hip).
+struct QueryArgs {
+    const rt_ray* rays;
+    rt_hit* hits;
+    long long count;
+    int width, height;
+    GPUCamera cam;
+    const GeometrySphere* spheres;
+    int sphere_count;
+    int scene_fast;
+    const GPUFace* faces;
+    const GPUVertex* vertices;
+    const GPUBVHNode* nodes;  // the mirror's private node array
+    const FlatTri* tris;
+    const float4 *pairs, *quads, *units, *tree, *ltris, *spairs, *flat;
+    const uint32_t* face_leaf;
+};
+// mode 17, 17 | LEAN_BIT or 21; occupancy 5, 6 or 7 waves per SIMD
+hipError_t launch_query(int stack, int mode, int waves_per_simd, const QueryArgs& q, hipStream_t s);
+
 // In librt_hip_exp.so (rt_exp.hip): exact alternatives kept for A/B measurement and their parity
 // tests, none of which serves the benchmark -- loading the library registers them (rt_render then
 // accepts the flags / knobs that select them; without it those requests are refused).

@@ -731,6 +731,20 @@ int rt_scene_mirror_face_leaf(rt_scene* s, uint32_t* leaf, size_t* count) {
     if (leaf) std::memcpy(leaf, m.face_leaf.data(), m.face_leaf.size() * 4);
     return 0;
 }
+int rt_scene_materials(rt_scene* s, void* out, size_t* count) {
+    if (!s || !count) {
+        rt_internal_set_error("rt_scene_materials: null argument");
+        return -1;
+    }
+    const std::vector<GPUMaterial> gm = s->scene.HostMaterials();
+    *count = gm.size();
+    if (out) {  // the fields; the struct's tail padding comes out as 0
+        std::memset(out, 0, gm.size() * sizeof(GPUMaterial));
+        for (size_t i = 0; i < gm.size(); i++)
+            std::memcpy((char*)out + i * sizeof(GPUMaterial), &gm[i], offsetof(GPUMaterial, IOR) + sizeof(float));
+    }
+    return 0;
+}
 void rt_scene_build(rt_scene* s) { s->scene.BuildHost(); }
 void rt_scene_camera(const rt_scene* s, GPUCamera* out) {
     *out = static_cast<const GPUCamera&>(const_cast<Scene&>(s->scene).GetCamera());

@@ -285,6 +285,77 @@ int rt_foreign_last_tracer(const GPUScene* scene);
  * library; rt_render refuses frames that ask for them otherwise.  0 otherwise. */
 int rt_experimental_loaded(void);
 
+/* ---------------------------------------------------------------------------------------
+ * Ray queries: "what does this ray hit?" for batches of rays, on the render kernel's own exact
+ * traversal (picking, visibility tests, depth / normal / albedo images, baking).
+ *
+ * Ray i gets exactly what the reference's GetRayHit(origin, direction) finds
+ * (main_raytracing.cu:83-109) with tmax as the initial closest distance (the renderer's own value
+ * is 1e30f): nd = normalize(direction); the sphere loop with strict <; BVHRayHit in the
+ * reference's right-first DFS order, the slab test on the direction as given, the primitive tests
+ * on nd; a triangle accepted when 0 <= t < best.
+ *
+ * PRECONDITION: direction is finite and not of zero length.  The slab test takes the direction
+ * unnormalised, as the reference does: a direction shorter than 1 makes box distances larger
+ * than the primitives' and may cull a node early (the reference's behaviour, inherited).
+ * rays and hits must be 16-byte aligned device memory; rt_ray.reserved must be 0 (it lives in
+ * device memory, so the call cannot check it; the kernel does not read it).
+ * ------------------------------------------------------------------------------------- */
+typedef struct rt_ray {
+    float origin[3];
+    float tmax;
+    float direction[3];
+    uint32_t reserved;
+} rt_ray; /* 32 B */
+
+/* kind: 0 miss, 1 sphere, 2 triangle.  id: sphere index or face index.  bx, by: glm's barycentrics
+ * (0 for spheres).  position = origin + nd * t.  normal, material: what the renderer shades with --
+ * spheres (position - centre) / radius; triangles the normalised v0.normal * bx + v1.normal * by +
+ * v2.normal * (1 - bx - by), flipped to face the ray (spheres are not flipped).
+ * A miss -- also a hit whose accepted distance is not < tmax, the reference's NaN rule -- has
+ * kind 0, t = tmax as passed and every other word 0, so whole buffers compare bytewise. */
+typedef struct rt_hit {
+    float t;
+    uint32_t kind;
+    uint32_t id;
+    uint32_t material;
+    float normal[3];
+    float bx;
+    float position[3];
+    float by;
+} rt_hit; /* 48 B */
+
+typedef struct rt_trace_params {
+    const rt_ray* rays;     /* DEVICE, count records; NULL = camera mode */
+    int64_t count;          /* rays (ignored in camera mode); 0 returns at once; at most 2^31 */
+    int32_t width, height;  /* camera mode only */
+    rt_hit* hits;           /* DEVICE, one record per ray */
+    uint32_t flags;         /* must be 0 */
+    int32_t waves_per_simd; /* occupancy build of the query kernel: 5 / 6 / 7, or 0 = the measured default
+                               (7; 5 for scenes with leaf trees, whose kernel spills at 6 and 7) */
+} rt_trace_params;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_ray) == 32 && offsetof(rt_ray, tmax) == 12 && offsetof(rt_ray, direction) == 16 &&
+              offsetof(rt_ray, reserved) == 28, "rt_ray");
+static_assert(sizeof(rt_hit) == 48 && offsetof(rt_hit, kind) == 4 && offsetof(rt_hit, id) == 8 &&
+              offsetof(rt_hit, material) == 12 && offsetof(rt_hit, normal) == 16 && offsetof(rt_hit, bx) == 28 &&
+              offsetof(rt_hit, position) == 32 && offsetof(rt_hit, by) == 44, "rt_hit");
+static_assert(sizeof(rt_trace_params) == 40 && offsetof(rt_trace_params, hits) == 24 &&
+              offsetof(rt_trace_params, flags) == 32, "rt_trace_params");
+#endif
+
+/* Trace a batch on `stream` (a hipStream_t, NULL = null stream): stream-ordered, no
+ * synchronisation, no allocation.  Camera mode (rays == NULL) traces width * height rays from the
+ * scene camera's origin through the pixel centres -- ray i is pixel (i % width, i / width),
+ * direction ((llc + h * ux) + v * uy) - origin with ux = ((float)x + 0.5f) / (float)width,
+ * uy = ((float)y + 0.5f) / (float)height, tmax 1e30f; set the camera with rt_scene_set_viewport
+ * before rt_scene_upload.  It reads no RNG state and writes no surface.
+ * The scene must have been uploaded by rt_scene_upload (whose rng_state may be NULL for a scene
+ * that is only queried); a GPUScene filled by another host is rejected.  Returns 0 or an error
+ * code with rt_last_error(). */
+int rt_trace_rays(const rt_trace_params* params, const GPUScene* scene, void* stream);
+
 /* init_rng for the pixels of one shard: state index s of shard (shard_index, shard_count)
  * of a width x height frame gets curand_init(seed, pixel_id(s), 0).  With shard_count == 1
  * the states are in y*width + x order (reference layout); otherwise they are compact in the
@@ -451,6 +522,9 @@ size_t rt_scene_host_arrays(const rt_scene* scene, const GPUBVHNode** nodes, siz
                             const uint32_t** face_indices, size_t* face_count, const GPUVertex** vertices,
                             size_t* vertex_count, const GPUFace** faces);
 int rt_scene_bvh_max_depth(const rt_scene* scene);
+/* Host copy of the scene's GPUMaterial array (what rt_hit.material indexes): *count receives the
+ * material count; out (may be NULL) receives the records.  0 or -1 with rt_last_error(). */
+int rt_scene_materials(rt_scene* scene, void* out, size_t* count);
 
 /* Build options (process-wide; affect later rt_scene_upload / mirror builds and
  * rt_bvh_build_device calls).  None of them changes a rendered bit -- the leaf trees and the GPU

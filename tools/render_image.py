@@ -2,6 +2,10 @@
 .pfm (linear) and .ppm (the reference viewer's tonemap).
 
     python tools/render_image.py [--config cfg2] [--frames 4] [--out gpurun_out/cfg2]
+    python tools/render_image.py --aov PREFIX
+
+--aov PREFIX also writes the first-hit images of the same camera (rt.gbuffer: pixel centres, no jitter) as
+PREFIX_normal.pfm (normal * 0.5 + 0.5), PREFIX_depth.pfm (hit distance, inf on a miss) and PREFIX_albedo.pfm.
 """
 import argparse
 import os
@@ -20,6 +24,7 @@ def main():
     ap.add_argument("--config", default="cfg2")
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "frame"))
+    ap.add_argument("--aov", default=None, metavar="PREFIX")
     args = ap.parse_args()
     rt = G.load_package()
     scene_name, W, H, SPP, BOUNCES, _ = bench.CONFIGS[args.config]
@@ -38,6 +43,15 @@ def main():
     rt.write_pfm(args.out + ".pfm", final, W, H)
     rt.write_ppm(args.out + ".ppm", rt.tonemap(final, W, H))
     print(f"wrote {args.out}.pfm / .ppm ({W}x{H}, {args.frames} frames x {SPP} spp)")
+    if args.aov:
+        g = rt.gbuffer(scene, W, H)
+        images = {"normal": g["normal"] * 0.5 + 0.5,
+                  "depth": g["depth"][:, :, None].expand(H, W, 3), "albedo": g["albedo"]}
+        os.makedirs(os.path.dirname(os.path.abspath(args.aov)), exist_ok=True)
+        for name, rgb in images.items():
+            rgba = torch.cat([rgb, torch.ones((H, W, 1), dtype=torch.float32, device=rgb.device)], dim=2)
+            rt.write_pfm(f"{args.aov}_{name}.pfm", rgba.reshape(H, W * 4), W, H)
+        print(f"wrote {args.aov}_normal.pfm / _depth.pfm / _albedo.pfm")
 
 
 if __name__ == "__main__":
