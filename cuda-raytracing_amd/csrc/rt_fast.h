@@ -456,8 +456,12 @@ __device__ __forceinline__ void offer(float t, uint32_t pos, uint32_t id, float 
         nan = true;
         return;
     }
-    if (t >= 0.0f && (t < h.best || (t == h.best && bpos != NO_POS && pos < bpos)))
-        h.best = t, h.kind = 2, h.id = id, h.bx = bx, h.by = by, bpos = pos;
+    // One predicate without short-circuit evaluation, then one branch.  Written as `t < h.best || (t == h.best &&
+    // ...)` in the `if`, the gfx950 build of the shared-leaf loop (quad_test) kept the previous face id when a
+    // candidate won on position at an equal distance, while taking its t, bx, by and position: a twin far from
+    // its triangle in leaf order exposes it (tests/test_gpu_adversarial.py).
+    const bool take = (t >= 0.0f) & ((t < h.best) | ((t == h.best) & (bpos != NO_POS) & (pos < bpos)));
+    if (take) h.best = t, h.kind = 2, h.id = id, h.bx = bx, h.by = by, bpos = pos;
 }
 
 // glm's test of triangle (v0, e1, e2) (test_triangle's operation order) offered at `pos`.
