@@ -14,6 +14,7 @@ Device buffers are torch tensors on the current HIP device (torch is plumbing he
 streams, torch.distributed); every kernel is in librt_hip.so.  There is no CPU fallback: if
 the native library is missing or fails to load this module raises.
 """
+import contextlib
 import ctypes
 import os
 
@@ -100,11 +101,24 @@ class TraceParams(ctypes.Structure):
                 ("hits", ctypes.c_void_p), ("flags", ctypes.c_uint32), ("waves_per_simd", ctypes.c_int32)]
 
 
+class DenoiseParams(ctypes.Structure):
+    """rt_denoise_params (rt_abi.h)."""
+    _fields_ = [("surface", ctypes.c_void_p), ("pitch", ctypes.c_uint64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("hits", ctypes.c_void_p), ("materials", ctypes.c_void_p), ("material_count", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("out", ctypes.c_void_p), ("out_pitch", ctypes.c_uint64),
+                ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_uint64), ("iterations", ctypes.c_int32),
+                ("normal_power_log2", ctypes.c_int32), ("sigma_plane", ctypes.c_float), ("sigma_color", ctypes.c_float)]
+
+
 HIT_MISS, HIT_SPHERE, HIT_TRIANGLE = 0, 1, 2  # rt_hit.kind
 RAY_TMAX = 1e30  # the renderer's own initial closest distance (main_raytracing.cu:85)
+DENOISE_DEFAULT = -1  # RT_DENOISE_DEFAULT: in a filter parameter of rt_denoise, the measured default
+# the defaults rt_denoise substitutes (csrc/denoise.hip; profiles/denoise_quality.txt)
+DENOISE_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_plane": 0.03, "sigma_color": 8.0}
 
 assert ctypes.sizeof(GPUScene) == 136 and ctypes.sizeof(GPUMaterial) == 64
 assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(Hit) == 48 and ctypes.sizeof(TraceParams) == 40
+assert ctypes.sizeof(DenoiseParams) == 96
 
 # name -> (restype, argtypes); every symbol include/rt_abi.h declares.
 _P, _I, _U32, _U64, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_size_t
@@ -114,6 +128,8 @@ SIGNATURES = {
     "init_rng": (None, [_U32, _U32, _P, ctypes.c_uint]),
     "rt_render": (_I, [ctypes.POINTER(RenderParams), _P, _P]),
     "rt_trace_rays": (_I, [ctypes.POINTER(TraceParams), _P, _P]),
+    "rt_denoise_scratch_bytes": (_SZ, [_I, _I]),
+    "rt_denoise": (_I, [ctypes.POINTER(DenoiseParams), _P]),
     "rt_foreign_mirror_wait": (_I, [_P]),
     "rt_foreign_last_tracer": (_I, [_P]),
     "rt_experimental_loaded": (_I, []),
@@ -561,6 +577,75 @@ def gbuffer(scene, width, height, stream=None, waves_per_simd=0):
             "kind": f["kind"].reshape(h, w).clone()}
 
 
+def denoise_scratch_bytes(width, height):
+    """rt_denoise_scratch_bytes: bytes of scratch rt_denoise needs for a width x height frame."""
+    return int(lib().rt_denoise_scratch_bytes(int(width), int(height)))
+
+
+def _allocating_on(stream):
+    """Context in which torch allocates (and fills) on `stream`; None = torch's current stream, as it is."""
+    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+
+
+def _denoise(surface, hits, materials_ptr, material_count, width, height, out, scratch, iterations, normal_power_log2,
+             sigma_plane, sigma_color, stream):
+    w, h = int(width), int(height)
+    assert surface.dtype == torch.float32 and surface.is_cuda and surface.dim() == 2 and surface.stride(1) == 1
+    assert surface.shape[0] >= h and surface.shape[1] >= 4 * w
+    assert hits.dtype == torch.float32 and hits.is_cuda and hits.is_contiguous() and hits.dim() == 2
+    assert hits.shape[1] == 12 and hits.shape[0] >= w * h
+    need = denoise_scratch_bytes(w, h)
+    # what is allocated here is allocated on the stream the kernels run on: the zero fill of `out` is ordered before
+    # them, and the caching allocator does not hand the scratch to another stream's work while they still run
+    with _allocating_on(stream):
+        if out is None:
+            out = alloc_surface(w, h, device=surface.device)
+        if scratch is None:
+            scratch = torch.empty((need // 4,), dtype=torch.float32, device=surface.device)
+    assert out.dtype == torch.float32 and out.is_cuda and out.dim() == 2 and out.stride(1) == 1
+    assert out.shape[0] >= h and out.shape[1] >= 4 * w
+    assert scratch.is_cuda and scratch.is_contiguous()
+    p = DenoiseParams()
+    p.surface, p.pitch = surface.data_ptr(), surface.stride(0) * 4
+    p.width, p.height = w, h
+    p.hits, p.materials, p.material_count = hits.data_ptr(), materials_ptr, int(material_count)
+    p.out, p.out_pitch = out.data_ptr(), out.stride(0) * 4
+    p.scratch, p.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
+    p.iterations, p.normal_power_log2 = int(iterations), int(normal_power_log2)
+    p.sigma_plane, p.sigma_color = float(sigma_plane), float(sigma_color)
+    _check(lib().rt_denoise(ctypes.byref(p), _stream_ptr(stream)), "rt_denoise")
+    return out
+
+
+def denoise_raw(surface, hits, materials, width, height, out=None, scratch=None, iterations=DENOISE_DEFAULT,
+                normal_power_log2=DENOISE_DEFAULT, sigma_plane=DENOISE_DEFAULT, sigma_color=DENOISE_DEFAULT, stream=None):
+    """rt_denoise on tensors only: `surface` a pitched float4 surface (alloc_surface), `hits` a float32 [H*W, 12]
+    tensor of rt_hit rows (record y*W + x, what trace_camera returns), `materials` a float32 CUDA tensor [M, 16]
+    of GPUMaterial rows (M may be 0).  Returns `out` (a new surface when None; `out is surface` is allowed).
+    `scratch`: any contiguous CUDA tensor of at least denoise_scratch_bytes(width, height) bytes, contents
+    irrelevant (allocated when None).  A filter parameter left at DENOISE_DEFAULT takes the library's default
+    (DENOISE_DEFAULTS).  Stream-ordered on `stream` (default: torch's current stream); tensors allocated here are
+    allocated on that stream, tensors passed in must be safe to use on it."""
+    assert materials.dtype == torch.float32 and materials.is_cuda and materials.is_contiguous()
+    assert materials.dim() == 2 and materials.shape[1] == 16
+    return _denoise(surface, hits, materials.data_ptr() if materials.shape[0] else None, materials.shape[0], width, height,
+                    out, scratch, iterations, normal_power_log2, sigma_plane, sigma_color, stream)
+
+
+def denoise(scene, surface, width, height, hits=None, out=None, scratch=None, iterations=DENOISE_DEFAULT,
+            normal_power_log2=DENOISE_DEFAULT, sigma_plane=DENOISE_DEFAULT, sigma_color=DENOISE_DEFAULT, stream=None):
+    """A viewable image from one low-sample frame of an uploaded Scene: rt_denoise guided by the camera's
+    first-hit records (`hits`, or trace_camera(scene, width, height) when None) and the scene's materials.
+    Returns `out` (a new surface when None).  Do not pass the tracer's last-frame surface as `out`: the
+    progressive accumulation would then average filtered colours."""
+    if hits is None:
+        with _allocating_on(stream):
+            hits = trace_camera(scene, width, height, stream=stream)
+    gpu = scene.gpu.contents if hasattr(scene, "gpu") else scene
+    return _denoise(surface, hits, gpu.gpu_materials, gpu.material_count, width, height, out, scratch, iterations,
+                    normal_power_log2, sigma_plane, sigma_color, stream)
+
+
 def foreign_mirror_wait(gpu_scene):
     """rt_foreign_mirror_wait: block until the background mirror build of a foreign GPUScene (a
     ctypes GPUScene filled by the caller) has finished; the next render installs it."""
@@ -792,6 +877,15 @@ class RayTracer:
         self.scene.set_viewport(self.width, self.height)
         self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
         return gbuffer(self.scene, self.width, self.height, stream=stream, waves_per_simd=waves_per_simd)
+
+    def denoised(self, **kw):
+        """A denoised copy of the current frame as a new pitched surface (module-level denoise(); **kw are its
+        filter parameters, hits, scratch, stream).  Uploads the scene like process(); `surface`, `last_frame`,
+        the RNG states and the frame index are left alone."""
+        assert "out" not in kw, "RayTracer.denoised returns a new surface"
+        self.scene.set_viewport(self.width, self.height)
+        self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
+        return denoise(self.scene, self.surface, self.width, self.height, **kw)
 
     def save(self, path):
         """The current frame: ``.pfm`` linear RGB, ``.ppm`` as the reference's viewer shows it

@@ -356,6 +356,84 @@ static_assert(sizeof(rt_trace_params) == 40 && offsetof(rt_trace_params, hits) =
  * code with rt_last_error(). */
 int rt_trace_rays(const rt_trace_params* params, const GPUScene* scene, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Denoising: a viewable image from one low-sample frame and the first-hit records of its camera
+ * (render -> rt_trace_rays in camera mode -> rt_denoise).  An edge-avoiding a-trous wavelet filter on
+ * the frame divided by the first hit's albedo, guided by normal, position and distance; the albedo
+ * is multiplied back in at the end, so texture edges are not blurred.
+ *
+ * The arithmetic is fixed (fp32, no contraction, IEEE division, only + - * /, fmaxf, fabsf and
+ * comparisons), so that tests/denoise_ref.py restates it bit for bit.  With p a pixel, record
+ * i = y * width + x of `hits`, valid(p) = hits[p].kind != 0 and dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z:
+ *
+ *  1. alb = materials[hits[p].material].albedo when valid(p) and material < material_count, else 1;
+ *     a = fmaxf(alb, 0.015625f); c = surface.rgb / a.  Alpha passes through untouched.
+ *  2. `iterations` passes s = 0.., step = 1 << s, each from the previous pass's colours.  !valid(p)
+ *     keeps c_p.  Otherwise for dy = -2..2 (outer), dx = -2..2 (inner), q = (x + dx*step, y + dy*step),
+ *     skipping q outside the image, !valid(q) and c_q.rgb not finite:
+ *       wn = fmaxf(0, dot(n_p, n_q)), squared normal_power_log2 times;
+ *       wz = fmaxf(0, 1 - fabsf(dot(n_p, pos_q - pos_p)) / (sigma_plane * t_p)), squared once
+ *            (t_p == 0 gives inf or NaN and so 0);
+ *       wc = 1 / (1 + dot(e, e) / (sc*sc)) with e = c_q - c_p, sc = sigma_color * 2^-s, when
+ *            sigma_color > 0 and c_p.rgb is finite, else 1;
+ *       w = (((h[dy+2] * h[dx+2]) * wn) * wz) * wc, h = {1/16, 1/4, 3/8, 1/4, 1/16};
+ *       if w > 0: sum += c_q * w, wsum += w.
+ *     out = wsum > 0 ? sum / wsum : c_p.
+ *  3. result = c * a.
+ *
+ * Rational weights instead of exp(): a correctly rounded division is the same on every host, expf is not.
+ *
+ * PITFALL: give the denoised image its own surface.  Written into rt_render's surface_last_frame it would
+ * feed filtered colours into the progressive accumulation.
+ * ------------------------------------------------------------------------------------- */
+#define RT_DENOISE_DEFAULT (-1)    /* in any of the four filter parameters: the measured default */
+#define RT_DENOISE_MAX_HEIGHT 131072      /* 2^17 rows (the launch grids hold a row of blocks per 4 pixel rows) */
+#define RT_DENOISE_MAX_PIXELS 1073741824  /* width * height at most 2^30 (64 GiB of scratch) */
+
+typedef struct rt_denoise_params {
+    const void* surface;           /* DEVICE pitched float4 frame, as rt_render writes it */
+    uint64_t pitch;                /* bytes per row of surface: >= width * 16, a multiple of 16 */
+    int32_t width, height;         /* > 0; height <= RT_DENOISE_MAX_HEIGHT, width * height <= RT_DENOISE_MAX_PIXELS */
+    const rt_hit* hits;            /* DEVICE width * height records of rt_trace_rays' camera mode */
+    const GPUMaterial* materials;  /* DEVICE (GPUScene.gpu_materials); may be NULL when material_count is 0 */
+    int32_t material_count;
+    int32_t flags;                 /* must be 0 */
+    void* out;                     /* DEVICE pitched float4 result; out == surface is allowed (below) */
+    uint64_t out_pitch;
+    void* scratch;                 /* DEVICE, rt_denoise_scratch_bytes(width, height); contents irrelevant */
+    uint64_t scratch_bytes;
+    /* Filter parameters.  RT_DENOISE_DEFAULT (-1, -1.0f) selects the default (profiles/denoise_quality.txt);
+     * 0 is a value of its own -- normal_power_log2 0 and sigma_color 0 switch their weight off, and
+     * iterations 0 and sigma_plane 0 are errors like every other value outside the range. */
+    int32_t iterations;            /* 1..6 (5): the last pass reaches 2 << (iterations - 1) pixels */
+    int32_t normal_power_log2;     /* 0..8 (5): the normal weight is cos^(2^this) */
+    float sigma_plane;             /* > 0 (0.03): tolerated distance from p's tangent plane, as a fraction of t_p */
+    float sigma_color;             /* >= 0 (8): colour distance (albedo-divided) that halves a tap at pass 0; 0 = off */
+} rt_denoise_params;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_denoise_params) == 96 &&offsetof(rt_denoise_params, pitch) == 8 &&
+              offsetof(rt_denoise_params, width) == 16 && offsetof(rt_denoise_params, hits) == 24 &&
+              offsetof(rt_denoise_params, materials) == 32 && offsetof(rt_denoise_params, material_count) == 40 &&
+              offsetof(rt_denoise_params, flags) == 44 && offsetof(rt_denoise_params, out) == 48 &&
+              offsetof(rt_denoise_params, out_pitch) == 56 && offsetof(rt_denoise_params, scratch) == 64 &&
+              offsetof(rt_denoise_params, scratch_bytes) == 72 && offsetof(rt_denoise_params, iterations) == 80 &&
+              offsetof(rt_denoise_params, normal_power_log2) == 84 && offsetof(rt_denoise_params, sigma_plane) == 88 &&
+              offsetof(rt_denoise_params, sigma_color) == 92,
+              "rt_denoise_params");
+#endif
+
+/* Bytes of scratch rt_denoise needs for a width x height frame (64 per pixel: the packed guide and two
+ * colour buffers); 0 for a size <= 0.  Monotone in both arguments. */
+size_t rt_denoise_scratch_bytes(int width, int height);
+/* Denoise on `stream` (a hipStream_t, NULL = null stream): stream-ordered, no synchronisation, no
+ * allocation; iterations + 1 kernel launches.  Every argument is checked on the host before the first
+ * launch (NULL pointers, sizes <= 0 or above the limits, pitches < width * 16, alignment, scratch too small,
+ * parameters out of range, flags != 0).  out == surface is safe: the first kernel consumes the whole surface into
+ * scratch, and the last pass, the only one that writes `out`, reads scratch and the material table only.
+ * `out` must not overlap scratch or hits.  Returns 0 or an error code with rt_last_error(). */
+int rt_denoise(const rt_denoise_params* params, void* stream);
+
 /* init_rng for the pixels of one shard: state index s of shard (shard_index, shard_count)
  * of a width x height frame gets curand_init(seed, pixel_id(s), 0).  With shard_count == 1
  * the states are in y*width + x order (reference layout); otherwise they are compact in the

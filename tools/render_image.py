@@ -3,9 +3,12 @@
 
     python tools/render_image.py [--config cfg2] [--frames 4] [--out gpurun_out/cfg2]
     python tools/render_image.py --aov PREFIX
+    python tools/render_image.py --denoise
 
 --aov PREFIX also writes the first-hit images of the same camera (rt.gbuffer: pixel centres, no jitter) as
 PREFIX_normal.pfm (normal * 0.5 + 0.5), PREFIX_depth.pfm (hit distance, inf on a miss) and PREFIX_albedo.pfm.
+--denoise also writes OUT_denoised.pfm / .ppm next to the beauty frame: rt.denoise of the last frame, guided by the
+same camera's first-hit records, into a surface of its own (the progressive history is not touched).
 """
 import argparse
 import os
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "frame"))
     ap.add_argument("--aov", default=None, metavar="PREFIX")
+    ap.add_argument("--denoise", action="store_true")
     args = ap.parse_args()
     rt = G.load_package()
     scene_name, W, H, SPP, BOUNCES, _ = bench.CONFIGS[args.config]
@@ -43,6 +47,11 @@ def main():
     rt.write_pfm(args.out + ".pfm", final, W, H)
     rt.write_ppm(args.out + ".ppm", rt.tonemap(final, W, H))
     print(f"wrote {args.out}.pfm / .ppm ({W}x{H}, {args.frames} frames x {SPP} spp)")
+    if args.denoise:
+        clean = rt.denoise(scene, final, W, H)
+        rt.write_pfm(args.out + "_denoised.pfm", clean, W, H)
+        rt.write_ppm(args.out + "_denoised.ppm", rt.tonemap(clean, W, H))
+        print(f"wrote {args.out}_denoised.pfm / .ppm")
     if args.aov:
         g = rt.gbuffer(scene, W, H)
         images = {"normal": g["normal"] * 0.5 + 0.5,
