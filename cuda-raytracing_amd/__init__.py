@@ -68,7 +68,7 @@ class BuildOptions(ctypes.Structure):
     """rt_build_options (rt_abi.h): exact-preserving speed knobs of the mirror / BVH builders."""
     _fields_ = [("leaf_tree_min", ctypes.c_uint32), ("cut_clusters", ctypes.c_uint32), ("cluster_max", ctypes.c_uint32),
                 ("split_angle", ctypes.c_float), ("bvh_small", ctypes.c_uint32), ("host_bvh", ctypes.c_int32),
-                ("leaf_screens", ctypes.c_int32)]
+                ("leaf_screens", ctypes.c_int32), ("entry_frontier", ctypes.c_int32)]
 
 
 class RenderParams(ctypes.Structure):
@@ -138,6 +138,7 @@ SIGNATURES = {
     "rt_unshard": (_I, [_P, _U64, _I, _I, _I, _P, ctypes.c_int64, _P]),
     "rt_shard_plan_capacity": (ctypes.c_int64, [_I, _I, _I]),
     "rt_shard_plan": (_I, [_I, _I, _I, _P, ctypes.c_int64, _P, _P]),
+    "rt_entry_table_builds": (_U64, []),
     "rt_get_build_options": (None, [_P]),
     "rt_set_build_options": (_I, [_P]),
     "rt_lane_plan_capacity": (ctypes.c_int64, [ctypes.c_int64]),
@@ -432,6 +433,11 @@ def mirror_build_check(nodes, face_indices, faces, vertices):
                                        faces.shape[0], vertices.ctypes.data, vertices.shape[0], meta.ctypes.data,
                                        ctypes.byref(tw)), "rt_mirror_build_check")
     return meta, bool(tw.value)
+
+
+def entry_table_builds():
+    """Entry tables rt_render has built so far in this process (rt_entry_table_builds)."""
+    return int(lib().rt_entry_table_builds())
 
 
 def bvh_build_device(vertices, faces, stream=None):

@@ -242,6 +242,23 @@ def build_host_driver(force=False):
     return HOST_DRIVER
 
 
+ENTRY_HOST_SRC = os.path.join(CSRC, "entry_host.cpp")
+ENTRY_HOST_LIB = os.path.join(PKG, "librt_entry_host.so")
+
+
+def build_entry_host(force=False):
+    """librt_entry_host.so: the host view of the entry-record builder for tests/test_entry_frontier.py (entry_host.h),
+    a test helper linked against librt_hip.so and kept out of it."""
+    deps = [ENTRY_HOST_SRC, LIB] + _deps(CSRC, (".h",)) + _deps(INC, (".h",))
+    if not force and _newer(ENTRY_HOST_LIB, deps):
+        return ENTRY_HOST_LIB
+    tmp = ENTRY_HOST_LIB + ".tmp"
+    _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", *FP_FLAGS, "-I", INC, "-I", CSRC, ENTRY_HOST_SRC, "-L", PKG,
+          "-l:librt_hip.so", "-Wl,-rpath,$ORIGIN", "-o", tmp])
+    os.replace(tmp, ENTRY_HOST_LIB)
+    return ENTRY_HOST_LIB
+
+
 def build_oracle(force=False):
     src = os.path.join(ORACLE_DIR, "rt_oracle.c")
     deps = [src, os.path.abspath(__file__)] + _deps(ORACLE_DIR, (".h",))
@@ -267,6 +284,7 @@ def build_reference_parts(force=False):
 
 def build_all(force=False):
     build_product(force)
+    build_entry_host(force)
     build_oracle(force)
     build_reference_parts(force)
     build_host_driver(force)

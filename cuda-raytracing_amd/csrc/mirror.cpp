@@ -8,6 +8,7 @@
 #include "leaftree.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -414,6 +415,7 @@ std::mutex g_mutex;
 std::map<const void*, Entry> g_mirrors;  // keyed by the device BVH node array
 
 void release(Entry& e) {
+    rt_internal_forget_entry_table(e.dev.nodes);  // the entry table built over this node array (rt_kernel.hip)
     if (e.block) rt_free(e.block);
     e.block = nullptr;
 }
@@ -451,6 +453,9 @@ int rt_internal_install_mirror(const GPUScene* s, const MirrorHost& m, bool owne
     e.dev.quads = at(8);
     e.dev.units = at(9);
     e.dev.face_leaf = at(10);
+    static std::atomic<uint64_t> generation{0};
+    e.dev.generation = ++generation;
+    e.dev.node_count = (uint32_t)(m.nodes.size() / 8);
     e.dev.depth = m.depth;
     e.dev.fast = m.fast;
     e.dev.screens = m.screens;
@@ -506,6 +511,7 @@ rt_build_options default_options() {
     o.bvh_small = 16;
     o.host_bvh = 0;
     o.leaf_screens = 0;  // measured slower (config 4), an opt-in A/B
+    o.entry_frontier = 0;  // exact; the frame time moved within run-to-run noise (profiles/entry_ab.txt), an opt-in
     return o;
 }
 rt_build_options g_options = default_options();
@@ -536,7 +542,7 @@ extern "C" int rt_set_build_options(const rt_build_options* o) {
     const rt_build_options v = o ? *o : default_options();
     if (v.leaf_tree_min < 2 || v.cut_clusters < 1 || v.cut_clusters > 32 || v.cluster_max < 1 || v.cluster_max > kClusterMax ||
         !(v.split_angle >= 0.0f && v.split_angle < 3.2f) || v.bvh_small < 2 || v.bvh_small > 64 || (v.host_bvh != 0 && v.host_bvh != 1) ||
-        (v.leaf_screens != 0 && v.leaf_screens != 1)) {
+        (v.leaf_screens != 0 && v.leaf_screens != 1) || (v.entry_frontier != 0 && v.entry_frontier != 1)) {
         rt_internal_set_error("rt_set_build_options: value out of range");
         return 1;
     }

@@ -120,6 +120,8 @@ struct MirrorDevice {
     int depth = -1;
     bool fast = false;
     int screens = 0;
+    uint32_t node_count = 0;   // nodes of the private array
+    uint64_t generation = 0;   // distinct for every installed mirror (the arrays' addresses can be reused)
     bool owned = true;         // built by rt_scene_upload, which forgets it before freeing the arrays
     uint64_t fingerprint = 0;  // foreign scenes: content hash of the arrays it was built from
 };
@@ -129,5 +131,8 @@ int rt_internal_install_mirror(const GPUScene* scene, const MirrorHost& m, bool 
                                uint64_t fingerprint = 0);  // 0 or -1 (rt_last_error)
 void rt_internal_forget_mirror(const void* gpu_nodes);
 bool rt_internal_lookup_mirror(const GPUScene* scene, MirrorDevice* out);
+
+// rt_kernel.hip: drops the camera rays' entry table (entry_frontier.h) built over a mirror's node array
+void rt_internal_forget_entry_table(const void* mirror_nodes);
 
 void rt_internal_set_error(const char* msg);  // rt_last_error() text (rt_kernel.hip)

@@ -1045,6 +1045,54 @@ __device__ __forceinline__ bool trav_begin(const float4* nodes4, const Ray& R, c
     return tmax >= tmin && tmin < h.best && tmax > 0.0f;
 }
 
+// trav_begin for a camera ray that has an entry record (entry_frontier.h: `rec` = count, then up to 15 nodes
+// in the reference's visit order, such that the reference's walk of this ray visits nothing outside their
+// subtrees).  IntersectAABB's `tmax >= tmin && tmax > 0` is applied to every node here, filtered like
+// inner_step's (classify_ok, the IEEE quotients when unsure); the passing ones go onto the lane's stack in
+// reverse visit order and the first is popped, so each is tested with `tmin < closest` (pop) at the point of
+// the walk where the reference pops it or the ancestor that keeps it out.  The root's own test is one of the
+// ancestors' tests.  At most 15 entries, all in LDS.  The stack gets DEEPER than the root walk's: where that holds one
+// pending sibling per level above the first record node, this holds up to 14 further record nodes, so under a
+// record node the stack reaches (EF_K - 1) + the scene's depth entries; launch_fast sizes the stack for it.
+// The whole record is read at once (one 64-B line) and parked in the lane's own stack column, entry j of n at
+// depth n - 1 - j; one loop then takes the entries from depth 0 up and writes the passing ones back from depth 0
+// (never above the one it reads).  Reading each entry from the record in global memory costs a dependent load
+// per entry and measured no gain; testing the entries straight-line (15 copies) was as fast as this loop but
+// 10 KB longer; flagging the entries for pop to test measured slower (profiles/entry_ab.txt).
+template <class S>
+__device__ __forceinline__ bool trav_begin_entry(const float4* nodes4, const S& stk, const uint32_t* rec, const Ray& R,
+                                                 const Hit& h, Trav& T) {
+    const int base = (int)threadIdx.x * 4;  // empty, own column
+    const uint4* rec4 = reinterpret_cast<const uint4*>(rec);
+    const uint4 q0 = rec4[0], q1 = rec4[1], q2 = rec4[2], q3 = rec4[3];
+    const uint32_t n = q0.x < 15u ? q0.x : 15u;
+    const int top = base + ((int)n - 1) * S::STEP;
+    auto park = [&](uint32_t j, uint32_t v) {
+        if (j < n) *stk.at(top - (int)j * S::STEP) = v;
+    };
+    park(0, q0.y), park(1, q0.z), park(2, q0.w), park(3, q1.x), park(4, q1.y), park(5, q1.z), park(6, q1.w), park(7, q2.x);
+    park(8, q2.y), park(9, q2.z), park(10, q2.w), park(11, q3.x), park(12, q3.y), park(13, q3.z), park(14, q3.w);
+    int sp = base;
+    for (int at = base; at <= top; at += S::STEP) {
+        const uint32_t idx = *stk.at(at);
+        const float4 lo = ldo(nodes4, 2 * idx), hi = ldo(nodes4, 2 * idx + 1);
+        float te, tx;
+        slab_approx(R, lo, hi, &te, &tx);
+        int co = R.fast ? classify_ok(te, tx) : UNSURE;
+        if (co == UNSURE) {
+            slab_exact(R, lo, hi, &te, &tx);
+            co = (tx >= te && tx > 0.0f) ? YES : NO;
+        }
+        if (co == YES) {
+            *stk.at(sp) = idx;
+            sp += S::STEP;
+        }
+    }
+    T.sp = sp;
+    return pop(nodes4, stk, T.sp, R, h.best, T.first, T.count);
+}
+constexpr uint32_t ENTRY_NONE = 0xffffffffu;  // trace: this lane's segment starts at the root
+
 // A big leaf's screen (mirror.h pf = 3, leaftree.h rt_build_leaf_screen), run by a lane when it
 // reaches the leaf: when cluster_cull proves that none of the leaf's core triangles can pass glm's
 // fp32 test with 0 <= t < closest for this ray, the sequential loop over the leaf
@@ -1475,16 +1523,25 @@ __device__ __forceinline__ void lone_traverse(const float4* nodes4, const float4
 // cooperative rounds); 1: pairs in the shared-leaf loop, scalar cooperative rounds; 2: scalar
 // records only.  MODE & 4: leaves with a leaf tree walk it (a statistics frame then counts the
 // reference's triangle tests plus the tree's own work).
-template <bool STATS, int MODE, class S, class C>
+// ENTRY (the lean render kernels): a lane whose `erec` is not ENTRY_NONE starts from record `erec` of the entry
+// table `etab` (trav_begin_entry) instead of the root.
+template <bool STATS, int MODE, bool ENTRY = false, class S, class C>
 __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, const float4* pairs,
                                       const float4* tree, const float4* ltris, const float4* flat,
                                       const float4* spairs, uint32_t tune_arg, const S& stk, uint32_t* scratch,
                                       Ray& R, Hit& h, bool live, C& c, const float4* quads = nullptr,
-                                      const float4* units = nullptr, const uint32_t* face_leaf = nullptr) {
+                                      const float4* units = nullptr, const uint32_t* face_leaf = nullptr,
+                                      const uint32_t* etab = nullptr, uint32_t erec = ENTRY_NONE) {
     constexpr bool LEAN = (MODE & LEAN_BIT) != 0;
     const uint32_t tune = LEAN ? 0u : tune_arg;
     Trav T{0, 0, 0};
-    bool active = live && trav_begin<STATS>(nodes4, R, h, T, c);
+    bool active = false;
+    if constexpr (ENTRY) {
+        if (live && erec != ENTRY_NONE) active = trav_begin_entry(nodes4, stk, etab + 16 * (size_t)erec, R, h, T);
+        else if (live) active = trav_begin<STATS>(nodes4, R, h, T, c);
+    } else {
+        active = live && trav_begin<STATS>(nodes4, R, h, T, c);
+    }
     // big-leaf screens (screen_leaf, MODE bit 5): split-step variants for scenes that have them
     constexpr bool scr_on = !STATS && (MODE & 16) != 0 && (MODE & 32) != 0;
     constexpr bool TIMING = (MODE & 8) != 0;

@@ -349,8 +349,19 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
             }
         }
         rtfast::Ray R = rtfast::make_ray(ro, rd, nd, A(&RenderArgs::scene_fast) != 0);
-        rtfast::trace<STATS, MODE>(nodes4, tris, a.pairs, a.tree, a.ltris, a.flat, a.spairs, a.tune, stk, scratch, R, h,
-                                   path, c, a.quads, a.units, a.face_leaf);
+        // Entry frontier (entry_frontier.h; the lean kernels): a camera ray inside the filtered range starts from
+        // its pixel's 8x8 sub-tile's record instead of the root.  The record follows from the lane's own pixel:
+        // with a lane map or a tile list the lanes of a wave belong to different sub-tiles.
+        constexpr bool ENTRY = LEAN && !STATS;
+        uint32_t erec = rtfast::ENTRY_NONE;
+        const uint32_t* etab = nullptr;
+        if constexpr (ENTRY) {
+            etab = A(&RenderArgs::entry);
+            if (etab && path && bounce == 0 && R.fast)
+                erec = (uint32_t)(y >> 3) * (uint32_t)((A(&RenderArgs::width) + 7) >> 3) + (uint32_t)(x >> 3);
+        }
+        rtfast::trace<STATS, MODE, ENTRY>(nodes4, tris, a.pairs, a.tree, a.ltris, a.flat, a.spairs, a.tune, stk, scratch, R, h,
+                                          path, c, a.quads, a.units, a.face_leaf, etab, erec);
         if (!path) continue;
 
         bool end = shade_segment<STATS, COLD>(a, h, ro, rd, nd, rng, color, thr, c);

@@ -35,6 +35,7 @@
 #include "rt_fast.h"
 
 #include "mirror.h"
+#include "entry_frontier.h"
 
 static_assert(MIRROR_BIG_LEAF == (uint32_t)rtfast::BIG, "pair records exist for exactly the big leaves");
 
@@ -250,8 +251,82 @@ hipError_t launch_prod(int stack, int mode, const RenderArgs& a, int waves, hipS
     return (m & rtfast::LEAN_BIT) ? launch_fast_lean(stack, m, a, waves, s) : launch_fast_prod(stack, m, a, waves, s);
 }
 
+// ---------------------------------------------------------------------------------------
+// Entry frontier (entry_frontier.h): per mirror, the device table of the camera rays' entry records and the key
+// it was built from.  entry_table returns the table for this frame's camera and viewport, rebuilding it on
+// `s` -- one lane per 8x8 sub-tile -- only when the key changed: a still camera pays nothing per frame, a moving
+// one the builder (2.7 ms at 1080p as it stands: profiles/entry_ab.txt) and never a host round trip (a new viewport
+// SIZE reallocates, which synchronises).  One
+// table per scene: frames of one scene rendered from different cameras on different streams at once would
+// race for it, as they would for the scene's RNG states.  A frame of the same key on another stream than the
+// one the table was built on waits for the build's event first.
+// ---------------------------------------------------------------------------------------
+static_assert(EF_K == 15 && EF_TILE == 8 && EF_WORDS == 16, "the lean kernels read 16-word records of 8x8 sub-tiles (rt_fast.h)");
+__global__ __launch_bounds__(64) void entry_table_kernel(const float* nodes, uint32_t node_count, EfCamera cam, int width,
+                                                         int height, int tiles_x, int tiles, uint32_t* out) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= tiles) return;
+    uint32_t rec[EF_WORDS];
+    ef_build_record(nodes, node_count, cam, width, height, i % tiles_x, i / tiles_x, rec);
+    uint4* o = reinterpret_cast<uint4*>(out + (size_t)EF_WORDS * i);
+    for (int k = 0; k < EF_WORDS / 4; k++) o[k] = make_uint4(rec[4 * k], rec[4 * k + 1], rec[4 * k + 2], rec[4 * k + 3]);
+}
+
+struct EntryTable {
+    EfKey key{};
+    bool valid = false;
+    uint32_t* dev = nullptr;
+    size_t bytes = 0;
+    hipEvent_t built = nullptr;  // recorded behind the builder on `built_on`
+    hipStream_t built_on = nullptr;
+};
+std::mutex g_entry_mutex;
+std::map<const void*, EntryTable> g_entry;  // keyed by the mirror's private node array
+std::atomic<uint64_t> g_entry_builds{0};
+
+// null (and the frame starts every ray at the root) when the table cannot be had
+const uint32_t* entry_table(const MirrorDevice& mir, const GPUCamera& c, int width, int height, hipStream_t s) {
+    EfCamera cam;
+    for (int i = 0; i < 3; i++) {
+        cam.origin[i] = c.origin[i], cam.lower_left[i] = c.lower_left_corner[i];
+        cam.horizontal[i] = c.horizontal[i], cam.vertical[i] = c.vertical[i];
+    }
+    const EfKey now = ef_make_key(cam, width, height, mir.nodes, mir.generation);
+    const int tiles_x = ef_tiles_x(width), tiles = tiles_x * ef_tiles_y(height);
+    const size_t bytes = (size_t)tiles * EF_WORDS * 4;
+    std::lock_guard<std::mutex> lock(g_entry_mutex);
+    EntryTable& t = g_entry[mir.nodes];
+    if (t.valid && ef_key_same(t.key, now)) {
+        if (s != t.built_on && hipStreamWaitEvent(s, t.built, 0) != hipSuccess) return nullptr;
+        return t.dev;
+    }
+    t.valid = false;
+    if (t.bytes != bytes) {
+        if (t.dev) (void)hipFree(t.dev);  // synchronises: no earlier frame still reads it
+        t.dev = nullptr, t.bytes = 0;
+        if (hipMalloc((void**)&t.dev, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            t.dev = nullptr;
+            return nullptr;
+        }
+        t.bytes = bytes;
+    }
+    hipLaunchKernelGGL(entry_table_kernel, dim3((unsigned)((tiles + 63) / 64)), dim3(64), 0, s, (const float*)mir.nodes,
+                       mir.node_count, cam, width, height, tiles_x, tiles, t.dev);
+    if (hipGetLastError() != hipSuccess) return nullptr;
+    if (!t.built && hipEventCreateWithFlags(&t.built, hipEventDisableTiming) != hipSuccess) return nullptr;
+    if (hipEventRecord(t.built, s) != hipSuccess) return nullptr;
+    t.built_on = s;
+    t.key = now, t.valid = true;
+    g_entry_builds++;
+    return t.dev;
+}
+
 hipError_t launch_fast(const RenderArgs& args, int waves, int depth, bool stats, hipStream_t s) {
-    const int stack = (depth >= 0 && depth + 2 <= 30) ? 30 : (depth >= 0 && depth + 2 <= 40) ? 40 : 64;
+    // a frame with an entry table starts a camera ray with up to EF_K record nodes on its stack, where the root walk
+    // holds one pending sibling per level: under the first of them the stack reaches (EF_K - 1) + depth entries
+    const int need = depth + 2 + (args.entry ? EF_K - 1 : 0);
+    const int stack = (depth >= 0 && need <= 30) ? 30 : (depth >= 0 && need <= 40) ? 40 : 64;
     // statistics: the reference's work on scalar records (RT_TUNE bit 7: through the leaf trees);
     // RT_TUNE bit 8: a timing frame of the production kernel instead (phase clocks, no counts)
     const ExperimentalKernels* x = g_experimental.load();  // rt_render refused these frames without it
@@ -868,6 +943,18 @@ extern "C" int rt_render(const rt_render_params* p, const GPUScene* scene, void*
         if (trav_nodes != (const GPUBVHNode*)mir.nodes) f.face_leaf = nullptr;
         return f;
     };
+    // Camera rays' entry records (entry_frontier.h): scenes with their own mirror inside the filtered range, on
+    // frames a lean kernel renders (lean_mode; not leaf-tree scenes, not the foreign / gated path)
+    {
+        rt_build_options bo;
+        rt_get_build_options(&bo);
+        const bool timing = stats ? (a.tune & 256u) != 0 : a.lane_cost != nullptr;
+        if (bo.entry_frontier && mir.owned && !gate && a.tris && !want_flat && !want_wf && !a.tree && !a.queue_head &&
+            !a.screens && scene_fast && (!stats || timing) && trav_nodes == (const GPUBVHNode*)mir.nodes &&
+            depth >= 0 && depth + 2 + (EF_K - 1) <= 64 &&  // the deepest stack a kernel has holds the record too (launch_fast)
+            (a.tune & 4096u) == 0 && ((a.tune >> 4) & 3u) < 2u && (lean_mode(trav(a), timing ? 25 : 17) & rtfast::LEAN_BIT))
+            a.entry = entry_table(mir, a.cam, p->width, p->height, s);
+    }
     hipError_t e;
     if (gate) {  // foreign scene with a mirror: exactly one of the two runs, by the frame's fingerprint
         a.gate = gate, a.gate_value = 1;
@@ -896,6 +983,17 @@ extern "C" int rt_render(const rt_render_params* p, const GPUScene* scene, void*
     } else
         e = launch_fast(trav(a), waves, depth, stats, s);
     return check(e, "render_kernel launch");
+}
+
+extern "C" uint64_t rt_entry_table_builds(void) { return g_entry_builds.load(); }
+
+void rt_internal_forget_entry_table(const void* mirror_nodes) {
+    std::lock_guard<std::mutex> lock(g_entry_mutex);
+    auto it = g_entry.find(mirror_nodes);
+    if (it == g_entry.end()) return;
+    if (it->second.dev) (void)hipFree(it->second.dev);
+    if (it->second.built) (void)hipEventDestroy(it->second.built);
+    g_entry.erase(it);
 }
 
 // Ray queries (rt_abi.h): argument checks, then the query kernel (rt_query.hip) in the variant a production

@@ -618,9 +618,18 @@ typedef struct rt_build_options {
     int32_t host_bvh;         /* 1: rt_scene_upload always builds the BVH on the host (0: GPU from 65,536 faces) */
     int32_t leaf_screens;     /* 1: big leaves whose core can be culled get a screen record (mirror.h pf = 3),
                                  rendered by the screen variants of librt_hip_exp.so (A/B, measured slower) (0) */
+    int32_t entry_frontier;   /* 1: the lean render kernels start camera rays from their 8x8 sub-tile's entry record
+                                 instead of the BVH root (csrc/entry_frontier.h); read by rt_render at every frame; same
+                                 frame bit for bit, a third fewer traversal steps per lane, frame time within noise (0) */
 } rt_build_options;
 void rt_get_build_options(rt_build_options* out);
 int rt_set_build_options(const rt_build_options* options);  /* 0, or an error for out-of-range values */
+
+/* Entry frontier (csrc/entry_frontier.h).  rt_render keeps, per uploaded scene, a device table of entry records
+ * -- one per 8x8 sub-tile of the viewport -- and rebuilds it, with one kernel on the render's stream, only when the
+ * camera, the viewport or the scene's node array changes.  rt_entry_table_builds counts those rebuilds
+ * (process-wide). */
+uint64_t rt_entry_table_builds(void);
 
 /* The reference's BVH builder (BVH::Calculate, RayTracing/BVH.cpp:8-124) run on the GPU over
  * device arrays: nodes and face indices byte-identical to the host builder (depth-first node
