@@ -203,6 +203,8 @@ SIGNATURES = {
     "rt_mirror_build_check": (_I, [_P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, ctypes.POINTER(ctypes.c_int)]),
     "rt_cluster_cull_host": (_I, [_P, _P, ctypes.c_float, _P]),
     "rt_twin_check_host": (_I, [_P, _P, _P]),
+    "rt_variant_host": (None, [_P, _P]),
+    "rt_family_has_mode_host": (_I, [_I, _I]),
     "rt_xorwow_jump_matrix": (_I, [_I, ctypes.POINTER(ctypes.c_uint32)]),
     "rt_xorwow_init_host": (None, [_U32, _U64, _P]),
 }

@@ -67,7 +67,7 @@ struct RenderArgs {
     const uint32_t* entry;  // camera rays' entry records, 16 words per 8x8 sub-tile of the viewport (entry_frontier.h), or null: off
     // Diagnostic A/B knobs (rt_render_params.tune; 0 = the production path, every setting exact):
     //   bit 0 no cooperative leaf rounds, 1 no pair records, 2 no leaf trees, 3 no small-leaf pairs,
-    //   4-5 big-leaf mode (launch_fast_t), 7 statistics through the leaf trees, 8 timing frame (phase
+    //   4-5 big-leaf mode (rt_variant.h), 7 statistics through the leaf trees, 8 timing frame (phase
     //   clocks), 9-10 occupancy override (1 compiler's choice, 2 = 6, 3 = 7 waves per SIMD),
     //   11 per-wave clock records, 12 no split small steps, 13-15 split threshold, 16-19 XCD run
     //   length (xcd_block), 20 no twin quads, 21-23 twin rounds' cooperative weight, 24 no deferred leaf trees, 26 no lone-ray traversal, 27 the reference's node array instead of the

@@ -6,7 +6,10 @@
 
 namespace rtk {
 namespace {
-const ExperimentalKernels kTable{launch_fast_ab, launch_fast_refill, launch_lone, launch_wavefront, launch_fast_screen};
+const ExperimentalKernels kTable{
+    {nullptr, nullptr, nullptr, nullptr, launch_fast_ab, launch_fast_ab2, launch_fast_refill, launch_fast_screen},
+    launch_lone, launch_wavefront};
+static_assert(FAM_AB == 4 && FAM_AB2 == 5 && FAM_REFILL == 6 && FAM_SCREEN == 7 && FAM_COUNT == 8, "kTable.fast's order");
 struct Registrar {
     Registrar() { register_experimental_kernels(&kTable, kExperimentalAbi); }
     ~Registrar() { register_experimental_kernels(nullptr, kExperimentalAbi); }

@@ -23,15 +23,11 @@
 //    same one.  Each lane still processes its nodes and leaves in the reference's DFS order.
 #pragma once
 
+#include "rt_variant.h"  // the names of MODE's bits (BIG_MASK ... LEAN_BIT), shared with the host's chooser
+
 namespace rtfast {
 
 constexpr int BIG = 8;     // leaves above this size wait for the wave (and have pair records)
-// MODE bit 7, the fixed-policy ("lean") production variants: RT_TUNE is the compile-time constant 0 and
-// every mirror array the variant uses is present (17: spairs, pairs, quads, units, tris; a leaf-tree mode
-// would add tree, ltris, flat, face_leaf -- none is built: rt_fast_lean.hip), so neither the knobs nor the
-// fallbacks for a missing array are compiled in.  rt_kernel.hip launch_fast routes a frame here only when
-// both hold.
-constexpr int LEAN_BIT = 128;
 constexpr int WAVE = 64;  // lane stride of the LDS stack
 
 using rtm::f3;
@@ -1053,7 +1049,7 @@ __device__ __forceinline__ bool trav_begin(const float4* nodes4, const Ray& R, c
 // the walk where the reference pops it or the ancestor that keeps it out.  The root's own test is one of the
 // ancestors' tests.  At most 15 entries, all in LDS.  The stack gets DEEPER than the root walk's: where that holds one
 // pending sibling per level above the first record node, this holds up to 14 further record nodes, so under a
-// record node the stack reaches (EF_K - 1) + the scene's depth entries; launch_fast sizes the stack for it.
+// record node the stack reaches (EF_K - 1) + the scene's depth entries; rt_variant.h choose_variant sizes the stack for it.
 // The whole record is read at once (one 64-B line) and parked in the lane's own stack column, entry j of n at
 // depth n - 1 - j; one loop then takes the entries from depth 0 up and writes the passing ones back from depth 0
 // (never above the one it reads).  Reading each entry from the record in global memory costs a dependent load
@@ -1136,7 +1132,7 @@ constexpr uint32_t DEFER_NONE = 0xffffffffu, DEFER_OFF = 0xfffffffeu, DEFER_END1
 constexpr int DEFER_WORDS = 5 * 64;
 template <int MODE>
 __device__ __forceinline__ uint32_t* defer_words(uint32_t* scratch) {
-    return scratch + ((MODE & 4) ? 64 : 0) + (threadIdx.x & 63u);
+    return scratch + ((MODE & TREE_BIT) ? 64 : 0) + (threadIdx.x & 63u);
 }
 
 __device__ __forceinline__ float next_up(float t) {  // the next float above t >= 0 (or -0)
@@ -1212,7 +1208,7 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
                                           unsigned long long big, bool waiting,
                                           const Ray& R, Hit& h, const Trav& T, C& c) {
     constexpr bool LEAN = (MODE & LEAN_BIT) != 0;  // fixed policy: tune == 0, every mirror array present (trace)
-    if ((MODE & 4) && (LEAN || tree)) {  // MODE bit 2: the scene has leaf trees
+    if ((MODE & TREE_BIT) && (LEAN || tree)) {  // MODE bit 2: the scene has leaf trees
         // lanes at leaves with a leaf tree (mirror.h: lead record pf == 2) walk it on their own
         bool at_tree = false;
         uint32_t root = 0;
@@ -1225,9 +1221,9 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
         if (mt) {
             if (!STATS && (LEAN || flat) && (tune & 0x40000000u) == 0)  // RT_TUNE bit 30: per-lane walk instead
             {
-                const unsigned long long tt0 = (MODE & 8) ? __builtin_amdgcn_s_memtime() : 0;
-                coop_tree<(MODE & 8) != 0>(tris, tree, ltris, flat, mt, root, R, h, T, scratch, tune, c);
-                if (MODE & 8) c.cy_tree += __builtin_amdgcn_s_memtime() - tt0;
+                const unsigned long long tt0 = (MODE & TIMING_BIT) ? __builtin_amdgcn_s_memtime() : 0;
+                coop_tree<(MODE & TIMING_BIT) != 0>(tris, tree, ltris, flat, mt, root, R, h, T, scratch, tune, c);
+                if (MODE & TIMING_BIT) c.cy_tree += __builtin_amdgcn_s_memtime() - tt0;
             }
             else if (at_tree)
                 tree_leaf<STATS>(tris, tree, ltris, root, T.first, T.count, R, h, c);
@@ -1247,7 +1243,7 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
         // the first record of a big leaf says where its pairs are, the second where its twin quads are (mirror.h)
         const f4v lead = ((ConstF4)(tris + 3 * (size_t)f0))[2];
         const uint32_t k = (uint32_t)__popcll(big);
-        if (!STATS && (MODE & 3) < 2 && (LEAN || quads) && (__float_as_uint(lead.w) & 1u)) {
+        if (!STATS && (MODE & BIG_MASK) < BIG_SCALAR && (LEAN || quads) && (__float_as_uint(lead.w) & 1u)) {
             // the second record: the leaf's first quad and quad count, the third: first unit and count
             const f4v l2 = ((ConstF4)(tris + 3 * (size_t)f0 + 3))[2];
             const f4v l3 = ((ConstF4)(tris + 3 * (size_t)f0 + 6))[2];
@@ -1257,12 +1253,12 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
             // RT_TUNE bits 21-23: the cooperative side's weight in quarters (0 = 4, the default)
             const uint32_t cw = (tune >> 21) & 7u;
             if (nu && (tune & 1u) == 0 && k * (70u * ((nu + 63u) / 64u) + 70u) * (cw ? cw : 4u) < 4u * 95u * nq) {
-                coop_units<(MODE & 8) != 0>(tris, units + 4 * (size_t)__float_as_uint(l3.z), nu, big, f0, c0, R, h, c);
-                if (MODE & 8) c.r_coop++, c.coop_rays += k;
+                coop_units<(MODE & TIMING_BIT) != 0>(tris, units + 4 * (size_t)__float_as_uint(l3.z), nu, big, f0, c0, R, h, c);
+                if (MODE & TIMING_BIT) c.r_coop++, c.coop_rays += k;
                 return waiting;
             }
             if (nq) {
-                if (MODE & 8) c.r_shared++;
+                if (MODE & TIMING_BIT) c.r_shared++;
                 const Hit h0 = h;
                 uint32_t bpos = NO_POS;
                 bool nan = !(h.best == h.best);
@@ -1270,9 +1266,9 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
                 for (uint32_t q = 0; q < nq; q++, qs += 7) {
                     const Pair P = make_pair(qs[0], qs[1], qs[2], qs[3], qs[4]);
                     const f4v bnd = qs[5];
-                    if (waiting) quad_test<(MODE & 8) != 0>(R.o, R.nd, P, bnd, qs + 6, h, bpos, nan, c);
+                    if (waiting) quad_test<(MODE & TIMING_BIT) != 0>(R.o, R.nd, P, bnd, qs + 6, h, bpos, nan, c);
                 }
-                if (MODE & 8) c.big_iters += nq;
+                if (MODE & TIMING_BIT) c.big_iters += nq;
                 if (waiting && nan) {  // the sequential loop from the entry distance (never taken for finite scenes)
                     h = h0;
                     leaf_sequential(tris, f0, c0, R.o, R.nd, h);
@@ -1280,20 +1276,20 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
                 return waiting;
             }
         }
-        if (!STATS && (MODE & 3) < 2 && (LEAN || pairs) && (__float_as_uint(lead.w) & 1u)) {
+        if (!STATS && (MODE & BIG_MASK) < BIG_SCALAR && (LEAN || pairs) && (__float_as_uint(lead.w) & 1u)) {
             const float4* lp = pairs + 5 * (size_t)__float_as_uint(lead.z);
             const uint32_t np = (c0 + 1u) / 2u, chunks = (np + 63u) / 64u;
             // cost model (VALU instructions per pair ~40): cooperative ~ k * (40 * chunks + 60),
             // shared-leaf ~ 40 * np for all waiting lanes at once
             const uint32_t cchunks = (c0 + 63u) / 64u;
-            if ((MODE & 3) == 0 && (tune & 1u) == 0 && k * (40u * chunks + 60u) < 40u * np) {
+            if ((MODE & BIG_MASK) == BIG_PAIRS && (tune & 1u) == 0 && k * (40u * chunks + 60u) < 40u * np) {
                 coop_leaf(tris, lp, big, f0, c0, R, h);
-                if (MODE & 8) c.r_coop++, c.coop_rays += k;
-            } else if ((MODE & 3) == 1 && (tune & 1u) == 0 && k * (60u * cchunks + 50u) < 40u * np) {
+                if (MODE & TIMING_BIT) c.r_coop++, c.coop_rays += k;
+            } else if ((MODE & BIG_MASK) == BIG_MIXED && (tune & 1u) == 0 && k * (60u * cchunks + 50u) < 40u * np) {
                 coop_leaf_scalar(tris, big, f0, c0, R, h);
-                if (MODE & 8) c.r_coop++, c.coop_rays += k;
+                if (MODE & TIMING_BIT) c.r_coop++, c.coop_rays += k;
             } else {
-                if (MODE & 8) c.r_shared++;
+                if (MODE & TIMING_BIT) c.r_shared++;
                 ConstF4 ps = (ConstF4)lp;
                 for (uint32_t q = 0; q < np; q++, ps += 5) {
                     const Pair P = ld_pair_scalar(ps, 0);
@@ -1519,10 +1515,10 @@ __device__ __forceinline__ void lone_traverse(const float4* nodes4, const float4
 
 // BVHRayHit for one lane (`live` = the lane has a segment to trace), every lane of the wave
 // calling.  Small steps run while any lane has one; big leaves wait until every lane is done
-// or waiting at one.  MODE & 3 -- 0: big leaves through pair records (shared-leaf loop and
-// cooperative rounds); 1: pairs in the shared-leaf loop, scalar cooperative rounds; 2: scalar
-// records only.  MODE & 4: leaves with a leaf tree walk it (a statistics frame then counts the
-// reference's triangle tests plus the tree's own work).
+// or waiting at one.  MODE & BIG_MASK -- BIG_PAIRS: big leaves through pair records (shared-leaf loop and
+// cooperative rounds); BIG_MIXED: pairs in the shared-leaf loop, scalar cooperative rounds; BIG_SCALAR: scalar
+// records only.  TREE_BIT: leaves with a leaf tree walk it (a statistics frame then counts the
+// reference's triangle tests plus the tree's own work).  The bits' names: rt_variant.h.
 // ENTRY (the lean render kernels): a lane whose `erec` is not ENTRY_NONE starts from record `erec` of the entry
 // table `etab` (trav_begin_entry) instead of the root.
 template <bool STATS, int MODE, bool ENTRY = false, class S, class C>
@@ -1543,17 +1539,17 @@ __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, 
         active = live && trav_begin<STATS>(nodes4, R, h, T, c);
     }
     // big-leaf screens (screen_leaf, MODE bit 5): split-step variants for scenes that have them
-    constexpr bool scr_on = !STATS && (MODE & 16) != 0 && (MODE & 32) != 0;
-    constexpr bool TIMING = (MODE & 8) != 0;
+    constexpr bool scr_on = !STATS && (MODE & SPLIT_BIT) != 0 && (MODE & SCREEN_BIT) != 0;
+    constexpr bool TIMING = (MODE & TIMING_BIT) != 0;
     // deferred big leaves (defer_leaf): production, timing and refill variants, not the screen ones; D = this
     // lane's words, or null when deferral is off (RT_TUNE bit 24).  Only the leaf-tree kernels defer: config 2's
     // 7-wave kernel spills 53 -> 186 dwords with the deferral compiled in.
-    constexpr bool DEFER = !STATS && (MODE & 32) == 0 && (MODE & 4) != 0;
+    constexpr bool DEFER = !STATS && (MODE & SCREEN_BIT) == 0 && (MODE & TREE_BIT) != 0;
     uint32_t* const D = (DEFER && (tune & (1u << 24)) == 0) ? defer_words<MODE>(scratch) : nullptr;
     if (D) D[0] = DEFER_NONE;
     unsigned long long t0 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
     for (;;) {
-        if constexpr ((MODE & 16) != 0) {
+        if constexpr ((MODE & SPLIT_BIT) != 0) {
             // split small steps: inner-node steps and small-leaf steps run in separate wave
             // iterations (a lane at a small leaf waits until at least half as many lanes are at
             // one as at inner nodes), so an iteration pays for one of the two code paths instead

@@ -1,7 +1,8 @@
 // rt_fast_body.h -- the production render kernel (rt_fast.h traversal + the per-lane segment loop)
 // and its launch helpers, included by the kernel translation units rt_fast_*.hip.  Each of those
 // instantiates one family of variants (production, timing, statistics, A/B, refill), so the
-// families compile in parallel; rt_kernel.hip picks the family and mode (rt_render.h).
+// families compile in parallel; rt_variant.h choose_variant picks the family and mode, rt_kernel.hip launches it
+// (rt_render.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -197,7 +198,7 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
     // refill_lanes takes that many entries with one atomic (ballot + mbcnt rank the idle lanes), so
     // lanes stay busy until the queue drains instead of idling once their own pixel is done.
     // Waves that start less than half full (split waves of a lane plan) are not refilled.
-    constexpr bool REFILL = (MODE & 64) != 0;  // refill is compiled into its own kernel variants only
+    constexpr bool REFILL = (MODE & rtfast::REFILL_BIT) != 0;  // refill is compiled into its own kernel variants only
     bool drained = !REFILL || a.queue_head == nullptr || __popcll(__ballot(pixel)) < 32;
     const long long qbase = (long long)gridDim.x * WAVE;
     Counters c;
@@ -212,11 +213,11 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
         if constexpr (COLD) return arg3<true>(a, offsetof(RenderArgs, cam) + off);
         else return loaded;
     };
-    const unsigned long long t_start = (MODE & 8) ? __builtin_amdgcn_s_memtime() : 0;
+    const unsigned long long t_start = (MODE & rtfast::TIMING_BIT) ? __builtin_amdgcn_s_memtime() : 0;
     // wave_clock and the per-wave (start, end) diagnostics use the device's constant 100 MHz clock
     // (s_memrealtime): one time base for every wave, also for a wave saved and restored by another
     // process sharing the GPU (the shader-cycle counter s_memtime is not)
-    const bool wave_times = (MODE & 8) && !LEAN && (a.tune & 2048u);  // RT_TUNE bit 11 (timing frames)
+    const bool wave_times = (MODE & rtfast::TIMING_BIT) && !LEAN && (a.tune & 2048u);  // RT_TUNE bit 11 (timing frames)
     const unsigned long long rt_start = (a.wave_clock || wave_times) ? __builtin_amdgcn_s_memrealtime() : 0;
 
 #ifdef RT_LIVE_HIST
@@ -298,14 +299,14 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
                 rs->v[3] = rng.v3;
                 rs->v[4] = rng.v4;
                 // per-pixel work for rt_lane_plan: traversal steps + 3 per big leaf + 1 per segment
-                if (MODE & 8) {
+                if (MODE & rtfast::TIMING_BIT) {
                     uint32_t* const lane_cost = A(&RenderArgs::lane_cost);
                     if (lane_cost) lane_cost[slot] = c.lane_work + (uint32_t)c.seg;
                 }
             }
         }
 #ifdef RT_LIVE_HIST  // diagnostic build (tools/lane_hist.sh LIVE=1): segment-loop wave cycles by live pixels
-        if (MODE & 8) {
+        if (MODE & rtfast::TIMING_BIT) {
             const unsigned long long tn = __builtin_amdgcn_s_memtime();
             if (lh_t) {
                 const unsigned long long dt = tn - lh_t;
@@ -322,7 +323,7 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
             if (drained) break;
             continue;  // every lane idle: refill at the top
         }
-        if (MODE & 8) c.w_iter++;
+        if (MODE & rtfast::TIMING_BIT) c.w_iter++;
         if (STATS) {
             c.w_seg += (threadIdx.x & 63) == 0;
             c.l_seg += path;
@@ -385,19 +386,19 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
     if (wave_clock && lane == 0) wave_clock[lb] = __builtin_amdgcn_s_memrealtime() - rt_start;
     unsigned long long* const stats = A(&RenderArgs::stats);
     unsigned long long lane_max = c.l_small;  // the busiest lane's small steps (timing frame)
-    if (MODE & 8)
+    if (MODE & rtfast::TIMING_BIT)
         for (int off = 32; off > 0; off >>= 1) {
             const unsigned long long o = __shfl_xor(lane_max, off);
             lane_max = o > lane_max ? o : lane_max;
         }
     unsigned long long lane_sum = c.l_small;  // the wave's lane-steps in small-step iterations (timing frame)
     unsigned long long big_sum[5] = {c.big_tests, c.tw_dec, c.tw_test, c.end2, c.redo};  // per lane -> the wave's
-    if ((MODE & 8) && stats)
+    if ((MODE & rtfast::TIMING_BIT) && stats)
         for (int off = 32; off > 0; off >>= 1) {
             lane_sum += __shfl_xor(lane_sum, off);
             for (int k = 0; k < 5; k++) big_sum[k] += __shfl_xor(big_sum[k], off);
         }
-    if ((MODE & 8) && stats && lane == 0) {  // timing frame: per-wave phase clocks
+    if ((MODE & rtfast::TIMING_BIT) && stats && lane == 0) {  // timing frame: per-wave phase clocks
         atomicAdd(stats + RT_STAT_CYCLES_SMALL, c.cy_small);
         atomicAdd(stats + RT_STAT_CYCLES_BIG, c.cy_big);
         atomicAdd(stats + RT_STAT_CYCLES_TOTAL, __builtin_amdgcn_s_memtime() - t_start);
@@ -458,38 +459,21 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
 // The production kernel.  The _w5 / _w6 / _w7 variants ask the compiler for 5 / 6 / 7 waves per
 // SIMD (fewer registers, more spilled) -- an occupancy / spill trade-off (RT_TUNE bits 9-10:
 // 0 = _w5, the default; 1 = unconstrained; 2 = _w6; 3 = _w7).
-template <int STACK, bool STATS, int MODE>
-__global__ __launch_bounds__(WAVE) void render_fast_kernel(RenderArgs a) {
-    constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL;  // LDS entries; deeper ones in `ovf` (rt_fast.h Stack)
-    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE];  // one word per entry (rt_fast.h pop)
-    __shared__ uint32_t scratch_lds[((MODE & 4) ? 64 : 0) + rtfast::DEFER_WORDS];  // coop_tree's compaction, deferred leaves
-    uint32_t ovf[STACK > SL ? STACK - SL : 1];
-    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds);
-}
-template <int STACK, bool STATS, int MODE>
-__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(5))) void render_fast_kernel_w5(RenderArgs a) {
-    constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL;  // LDS entries; deeper ones in `ovf` (rt_fast.h Stack)
-    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE];  // one word per entry (rt_fast.h pop)
-    __shared__ uint32_t scratch_lds[((MODE & 4) ? 64 : 0) + rtfast::DEFER_WORDS];  // coop_tree's compaction, deferred leaves
-    uint32_t ovf[STACK > SL ? STACK - SL : 1];
-    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds);
-}
-template <int STACK, bool STATS, int MODE>
-__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(6))) void render_fast_kernel_w6(RenderArgs a) {
-    constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL;  // LDS entries; deeper ones in `ovf` (rt_fast.h Stack)
-    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE];  // one word per entry (rt_fast.h pop)
-    __shared__ uint32_t scratch_lds[((MODE & 4) ? 64 : 0) + rtfast::DEFER_WORDS];  // coop_tree's compaction, deferred leaves
-    uint32_t ovf[STACK > SL ? STACK - SL : 1];
-    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds);
-}
-template <int STACK, bool STATS, int MODE>
-__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7))) void render_fast_kernel_w7(RenderArgs a) {
-    constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL;  // LDS entries; deeper ones in `ovf` (rt_fast.h Stack)
-    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE];  // one word per entry (rt_fast.h pop)
-    __shared__ uint32_t scratch_lds[((MODE & 4) ? 64 : 0) + rtfast::DEFER_WORDS];  // coop_tree's compaction, deferred leaves
-    uint32_t ovf[STACK > SL ? STACK - SL : 1];
-    render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds);
-}
+#define RT_FAST_KERNEL(NAME, ...) \
+    template <int STACK, bool STATS, int MODE> \
+    __global__ __launch_bounds__(WAVE) __VA_ARGS__ void NAME(RenderArgs a) { \
+        constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL; /* LDS entries; deeper ones in `ovf` (rt_fast.h Stack) */ \
+        __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE]; /* one word per entry (rt_fast.h pop) */ \
+        /* coop_tree's compaction, deferred leaves */ \
+        __shared__ uint32_t scratch_lds[((MODE & rtfast::TREE_BIT) ? 64 : 0) + rtfast::DEFER_WORDS]; \
+        uint32_t ovf[STACK > SL ? STACK - SL : 1]; \
+        render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds); \
+    }
+RT_FAST_KERNEL(render_fast_kernel, )
+RT_FAST_KERNEL(render_fast_kernel_w5, __attribute__((amdgpu_waves_per_eu(5))))
+RT_FAST_KERNEL(render_fast_kernel_w6, __attribute__((amdgpu_waves_per_eu(6))))
+RT_FAST_KERNEL(render_fast_kernel_w7, __attribute__((amdgpu_waves_per_eu(7))))
+#undef RT_FAST_KERNEL
 
 // Waves of `kernel` the device holds at once (refill launches size their grid to it).
 template <class K>
@@ -546,7 +530,7 @@ hipError_t launch_grid(K kernel, const RenderArgs& args, int waves, bool refill,
 // RT_TUNE bits 9-10 = 2 / 3).  rt_render rejects the retired RT_TUNE override 1 (compiler's choice).
 template <int STACK, bool STATS, int MODE>
 hipError_t launch_occ(const RenderArgs& args, int waves, hipStream_t stream) {
-    constexpr bool refill = (MODE & 64) != 0;  // only these variants drain a refill queue
+    constexpr bool refill = (MODE & rtfast::REFILL_BIT) != 0;  // only these variants drain a refill queue
     if constexpr (STATS) {
         return launch_grid(render_fast_kernel<STACK, true, MODE>, args, waves, refill, stream);
     } else {
@@ -575,12 +559,20 @@ hipError_t launch_occ(const RenderArgs& args, int waves, hipStream_t stream) {
 // by the first option (cluster_cull's `best == best` test) added the second path into the join that made
 // the copy necessary.  build.py's guard rejects any object with vector instructions in such a narrowed
 // flow block.
-#define RT_FAST_FAMILY(NAME, DISPATCH) \
+//
+// RT_APPLY(RT_FAST_FAMILY, RT_FAMILY_x) defines the launcher of row x of rt_render.h's table.
+template <int STACK, bool STATS, int... MODES>
+hipError_t launch_mode(int mode, const RenderArgs& a, int waves, hipStream_t s) {
+    hipError_t e = hipErrorInvalidValue;  // a mode the row does not hold
+    (void)((mode == MODES && ((e = launch_occ<STACK, STATS, MODES>(a, waves, s)), true)) || ...);
+    return e;
+}
+#define RT_FAST_FAMILY(FAM, NAME, STATS, ...) \
     hipError_t NAME(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s) { \
         switch (stack) { \
-            case 30: return DISPATCH<30>(mode, a, waves, s); \
-            case 40: return DISPATCH<40>(mode, a, waves, s); \
-            default: return DISPATCH<64>(mode, a, waves, s); \
+            case 30: return launch_mode<30, STATS, __VA_ARGS__>(mode, a, waves, s); \
+            case 40: return launch_mode<40, STATS, __VA_ARGS__>(mode, a, waves, s); \
+            default: return launch_mode<64, STATS, __VA_ARGS__>(mode, a, waves, s); \
         } \
     }
 

@@ -213,43 +213,12 @@ const uint32_t* device_jump_table() {
     return d;
 }
 
-// The render kernel variant of a frame: the traversal stack of the scene's BVH depth (the DFS holds
-// at most depth + 1 entries; 30 entries -- 7.5 KB of LDS per wave -- still fits 5 waves per SIMD and
-// covers the 4-bunny scene's depth 28), then the MODE bits (rt_fast_body.h render_fast_body), then
-// the translation unit that holds that family (rt_render.h).
-std::atomic<const ExperimentalKernels*> g_experimental{nullptr};
-
-// Whether a frame asks for a kernel of librt_hip_exp.so (rt_render.h): the non-split / big-leaf
-// A/B variants (RT_TUNE bits 12, 4-5), refill, the lone-pixel kernel, the wavefront tracer.
-bool needs_experimental(const rt_render_params* p, bool has_tree, bool screens) {
-    const bool stats = (p->flags & RT_RENDER_STATS) != 0;
-    if ((p->flags & RT_RENDER_TRACER_WAVEFRONT) || p->refill_lanes || p->lone_count > 0) return true;
-    if (screens && (p->tune & 4096u) == 0 && (!stats || (p->tune & 256u))) return true;  // big-leaf screen variants
-    if (stats || p->lane_cost) return false;  // statistics / timing families are in the product
-    const uint32_t mode = (p->tune >> 4) & 3u;
-    return (p->tune & 4096u) != 0 || (!has_tree && (mode == 2u || mode == 3u));
-}
-
-// RT_TUNE bits a render kernel itself reads (rt_fast.h trace / big_round / coop_tree: bits 0, 13-15, 21-24, 26,
-// 30, 31; rt_fast_body.h: the XCD run length 16-19, the per-wave clock records 11).  The others choose a
-// kernel or drop a mirror array on the host.
-constexpr uint32_t kKernelTuneBits = 1u | (1u << 11) | (7u << 13) | (15u << 16) | (7u << 21) | (1u << 24) | (1u << 26) |
-                                     (1u << 30) | (1u << 31);
-
-// MODE 17 (or its timing variant 25) with the lean bit (rt_fast.h LEAN_BIT) when the frame sets no knob the
-// kernel reads and the scene's mirror holds every array that variant assumes; `mode` itself otherwise, and for
-// the leaf-tree modes 21 / 29, which have no lean variant (rt_fast_lean.hip: measured slower).
-int lean_mode(const RenderArgs& a, int mode) {
-    if ((mode & 4) || (a.tune & kKernelTuneBits)) return mode;
-    const bool have = a.nodes && a.tris && a.spairs && a.pairs && a.quads && a.units;
-    return have ? mode | rtfast::LEAN_BIT : mode;
-}
-
-// The production variant `mode` (17 / 21): the lean kernel when lean_mode allows it, else the general one.
-hipError_t launch_prod(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s) {
-    const int m = lean_mode(a, mode);
-    return (m & rtfast::LEAN_BIT) ? launch_fast_lean(stack, m, a, waves, s) : launch_fast_prod(stack, m, a, waves, s);
-}
+// The launch table of render_fast_body's families (rt_render.h), indexed by Family: the product's rows filled in
+// here, the plugin's by register_experimental_kernels (null, and rt_render refuses the frame, until then).
+std::atomic<FastLauncher> g_family[FAM_COUNT] = {{launch_fast_prod}, {launch_fast_lean}, {launch_fast_timing},
+                                                 {launch_fast_stats}};
+static_assert(FAM_PROD == 0 && FAM_LEAN == 1 && FAM_TIMING == 2 && FAM_STATS == 3 && FAM_AB == 4, "g_family's order");
+std::atomic<const ExperimentalKernels*> g_experimental{nullptr};  // the plugin's table: its lone-pixel and wavefront paths
 
 // ---------------------------------------------------------------------------------------
 // Entry frontier (entry_frontier.h): per mirror, the device table of the camera rays' entry records and the key
@@ -322,45 +291,11 @@ const uint32_t* entry_table(const MirrorDevice& mir, const GPUCamera& c, int wid
     return t.dev;
 }
 
-hipError_t launch_fast(const RenderArgs& args, int waves, int depth, bool stats, hipStream_t s) {
-    // a frame with an entry table starts a camera ray with up to EF_K record nodes on its stack, where the root walk
-    // holds one pending sibling per level: under the first of them the stack reaches (EF_K - 1) + depth entries
-    const int need = depth + 2 + (args.entry ? EF_K - 1 : 0);
-    const int stack = (depth >= 0 && need <= 30) ? 30 : (depth >= 0 && need <= 40) ? 40 : 64;
-    // statistics: the reference's work on scalar records (RT_TUNE bit 7: through the leaf trees);
-    // RT_TUNE bit 8: a timing frame of the production kernel instead (phase clocks, no counts)
-    const ExperimentalKernels* x = g_experimental.load();  // rt_render refused these frames without it
-    // MODE bit 5 (librt_hip_exp.so): big-leaf screens, for scenes whose mirror has screen records
-    const bool scr = args.screens != 0 && (args.tune & 4096u) == 0;
-    if (stats && (args.tune & 256u)) {
-        if (scr) return x ? x->fast_screen(stack, args.tree ? 61 : 57, args, waves, s) : hipErrorNotSupported;
-        if (!args.tree && (args.tune & 4096u)) return launch_fast_timing(stack, 9, args, waves, s);
-        return launch_fast_timing(stack, lean_mode(args, args.tree ? 29 : 25), args, waves, s);
-    }
-    // per-pixel work (rt_render_params.lane_cost): the timing variant of the production kernel
-    if (!stats && args.lane_cost) {
-        if (scr) return x ? x->fast_screen(stack, args.tree ? 61 : 57, args, waves, s) : hipErrorNotSupported;
-        return launch_fast_timing(stack, lean_mode(args, args.tree ? 29 : 25), args, waves, s);
-    }
-    if (stats) return launch_fast_stats(stack, (args.tree && (args.tune & 128u)) ? 6 : 2, args, waves, s);
-    // MODE bit 4: inner-node and small-leaf steps in separate iterations (rt_fast.h trace); RT_TUNE
-    // bit 12 turns it off (A/B).  Big leaves: packed pairs in the shared-leaf loop, scalar records in
-    // cooperative rounds (MODE 1, measured best); leaf trees compiled in only for scenes that have
-    // them (MODE bit 2); A/B: RT_TUNE bits 4-5 = 2 scalar only, 3 pairs everywhere.
-    const bool split = (args.tune & 4096u) == 0;
-    if (args.queue_head) return x ? x->fast_refill(stack, args.tree ? 85 : 81, args, waves, s) : hipErrorNotSupported;
-    if (scr && split && (args.tree || ((args.tune >> 4) & 3u) < 2u))
-        return x ? x->fast_screen(stack, args.tree ? 53 : 49, args, waves, s) : hipErrorNotSupported;
-    if (args.tree) {
-        if (split) return launch_prod(stack, 21, args, waves, s);
-        return x ? x->fast_ab(stack, 5, args, waves, s) : hipErrorNotSupported;
-    }
-    const uint32_t mode = (args.tune >> 4) & 3u;
-    if (split && mode < 2) return launch_prod(stack, 17, args, waves, s);
-    if (!x) return hipErrorNotSupported;
-    if (mode == 2) return x->fast_ab(stack, 2, args, waves, s);
-    if (mode == 3) return x->fast_ab(stack, 0, args, waves, s);
-    return x->fast_ab(stack, 1, args, waves, s);
+static_assert(kEntryStackExtra == EF_K - 1, "rt_variant.h sizes the stack of a frame with entry records");
+
+hipError_t launch_fast(const Variant& v, const RenderArgs& args, int waves, hipStream_t s) {
+    const FastLauncher f = g_family[v.family].load();
+    return f ? f(v.stack, v.mode, args, waves, s) : hipErrorNotSupported;  // rt_render refused these frames without the plugin
 }
 
 }  // namespace
@@ -374,6 +309,7 @@ void rtk::register_experimental_kernels(const rtk::ExperimentalKernels* k, uint3
         return;
     }
     g_experimental.store(k);
+    for (int f = rtk::FAM_AB; f < rtk::FAM_COUNT; f++) g_family[f].store(k ? k->fast[f] : nullptr);  // the plugin's rows
 }
 const rtk::ExperimentalKernels* rtk::experimental_kernels() { return g_experimental.load(); }
 
@@ -908,7 +844,23 @@ extern "C" int rt_render(const rt_render_params* p, const GPUScene* scene, void*
     if (want_wf && (p->spp > 65535 || p->bounces > 255 || (int64_t)p->spp * p->bounces > 65536))
         return set_error("rt_render: the wavefront tracer needs spp <= 65535, bounces <= 255, spp x bounces <= 65536");
     a.screens = (mir.screens > 0 && (a.tune & (1u << 28)) == 0 && a.tris && !(p->flags & RT_RENDER_TRACER_FLAT)) ? 1 : 0;
-    if (!g_experimental.load() && needs_experimental(p, a.tree != nullptr, a.screens != 0))
+    // the traversal kernels read the mirror's private node array (mirror.h: 64-B aligned sibling
+    // pairs in right-first pre-order; RT_TUNE bit 27: the reference's array instead, A/B); the
+    // reference-layout tracers keep the reference's
+    const GPUBVHNode* const trav_nodes =
+        (mir.nodes && (a.tune & (1u << 27)) == 0) ? (const GPUBVHNode*)mir.nodes : scene->gpu_bvh_nodes;
+    // Camera rays' entry records (entry_frontier.h): scenes with their own mirror inside the filtered range, not the
+    // foreign / gated path -- on the frames choose_variant gives a lean kernel
+    rt_build_options bo;
+    rt_get_build_options(&bo);
+    const bool want_entry = bo.entry_frontier && mir.owned && !gate && a.tris && !want_flat && !want_wf && scene_fast &&
+                            trav_nodes == (const GPUBVHNode*)mir.nodes;
+    // the production tracer's kernel for this frame (rt_variant.h; the fields in VariantInput's order); the wavefront
+    // tracer and the lone-pixel kernel are paths of their own, in the plugin as well
+    const bool arrays_complete = a.nodes && a.tris && a.spairs && a.pairs && a.quads && a.units;
+    Variant v = choose_variant({a.tune, stats, a.lane_cost != nullptr, a.refill_lanes != 0, a.tree != nullptr, a.screens != 0,
+                                arrays_complete, depth, want_entry});
+    if (!g_experimental.load() && (want_wf || p->lone_count > 0 || v.needs_plugin))
         return set_error("rt_render: this frame asks for an experimental render path (wavefront tracer, refill, lone-pixel "
                          "kernel or an RT_TUNE A/B variant), which lives in librt_hip_exp.so -- load it first "
                          "(rt.load_experimental())");
@@ -930,11 +882,6 @@ extern "C" int rt_render(const rt_render_params* p, const GPUScene* scene, void*
         if (check(hipMemsetAsync(a.queue_head, 0, sizeof(unsigned long long), s), "hipMemsetAsync") != 0) return 1;
     }
     a.scene_fast = scene_fast ? 1 : 0;
-    // the traversal kernels read the mirror's private node array (mirror.h: 64-B aligned sibling
-    // pairs in right-first pre-order; RT_TUNE bit 27: the reference's array instead, A/B); the
-    // reference-layout tracers keep the reference's
-    const GPUBVHNode* const trav_nodes =
-        (mir.nodes && (a.tune & (1u << 27)) == 0) ? (const GPUBVHNode*)mir.nodes : scene->gpu_bvh_nodes;
     auto trav = [&](const RenderArgs& x) {  // the arguments as they stand at launch, traversal nodes
         RenderArgs f = x;
         f.nodes = trav_nodes;
@@ -943,22 +890,12 @@ extern "C" int rt_render(const rt_render_params* p, const GPUScene* scene, void*
         if (trav_nodes != (const GPUBVHNode*)mir.nodes) f.face_leaf = nullptr;
         return f;
     };
-    // Camera rays' entry records (entry_frontier.h): scenes with their own mirror inside the filtered range, on
-    // frames a lean kernel renders (lean_mode; not leaf-tree scenes, not the foreign / gated path)
-    {
-        rt_build_options bo;
-        rt_get_build_options(&bo);
-        const bool timing = stats ? (a.tune & 256u) != 0 : a.lane_cost != nullptr;
-        if (bo.entry_frontier && mir.owned && !gate && a.tris && !want_flat && !want_wf && !a.tree && !a.queue_head &&
-            !a.screens && scene_fast && (!stats || timing) && trav_nodes == (const GPUBVHNode*)mir.nodes &&
-            depth >= 0 && depth + 2 + (EF_K - 1) <= 64 &&  // the deepest stack a kernel has holds the record too (launch_fast)
-            (a.tune & 4096u) == 0 && ((a.tune >> 4) & 3u) < 2u && (lean_mode(trav(a), timing ? 25 : 17) & rtfast::LEAN_BIT))
-            a.entry = entry_table(mir, a.cam, p->width, p->height, s);
-    }
+    if (v.use_entry && !(a.entry = entry_table(mir, a.cam, p->width, p->height, s)))
+        v.use_entry = false, v.stack = variant_stack(depth);  // no table: every ray from the root
     hipError_t e;
     if (gate) {  // foreign scene with a mirror: exactly one of the two runs, by the frame's fingerprint
         a.gate = gate, a.gate_value = 1;
-        e = want_flat ? launch_ref_tracer(true, a, tiles * 4, depth, stats, s) : launch_fast(trav(a), waves, depth, stats, s);
+        e = want_flat ? launch_ref_tracer(true, a, tiles * 4, depth, stats, s) : launch_fast(v, trav(a), waves, s);
         if (e == hipSuccess) {
             RenderArgs r = a;
             r.tris = nullptr, r.gate_value = 0;
@@ -977,11 +914,11 @@ extern "C" int rt_render(const rt_render_params* p, const GPUScene* scene, void*
         if (check(hipEventRecord(ls->fork, s), "hipEventRecord") || check(hipStreamWaitEvent(ls->side, ls->fork, 0), "hipStreamWaitEvent"))
             return 1;
         e = g_experimental.load()->lone(a, p->lone_slots, (int)p->lone_count, mir.treelets, ls->side);
-        if (e == hipSuccess) e = launch_fast(trav(a), waves, depth, stats, s);
+        if (e == hipSuccess) e = launch_fast(v, trav(a), waves, s);
         if (check(hipEventRecord(ls->join, ls->side), "hipEventRecord") || check(hipStreamWaitEvent(s, ls->join, 0), "hipStreamWaitEvent"))
             return 1;
     } else
-        e = launch_fast(trav(a), waves, depth, stats, s);
+        e = launch_fast(v, trav(a), waves, s);
     return check(e, "render_kernel launch");
 }
 
@@ -997,7 +934,7 @@ void rt_internal_forget_entry_table(const void* mirror_nodes) {
 }
 
 // Ray queries (rt_abi.h): argument checks, then the query kernel (rt_query.hip) in the variant a production
-// frame of this scene runs at RT_TUNE 0 -- the choices of launch_fast and lean_mode.  Stream-ordered: no
+// frame of this scene runs at RT_TUNE 0 (choose_variant).  Stream-ordered: no
 // synchronisation, no allocation.
 extern "C" int rt_trace_rays(const rt_trace_params* p, const GPUScene* scene, void* stream) {
     if (!p) return set_error("rt_trace_rays: null params");
@@ -1042,14 +979,13 @@ extern "C" int rt_trace_rays(const rt_trace_params* p, const GPUScene* scene, vo
     q.tree = (const float4*)mir.tree, q.ltris = (const float4*)mir.ltris, q.spairs = (const float4*)mir.spairs;
     q.flat = (const float4*)mir.flat;
     q.face_leaf = (const uint32_t*)mir.face_leaf;
-    const int depth = mir.depth;
-    const int stack = (depth >= 0 && depth + 2 <= 30) ? 30 : (depth >= 0 && depth + 2 <= 40) ? 40 : 64;
-    int mode = q.tree ? 21 : 17;
-    if (mode == 17 && q.spairs && q.pairs && q.quads && q.units) mode |= rtfast::LEAN_BIT;  // lean_mode's conditions
+    VariantInput in{};  // tune 0, no statistics / lane_cost / refill / screens / entry records
+    in.has_tree = q.tree != nullptr, in.arrays_complete = q.spairs && q.pairs && q.quads && q.units, in.depth = mir.depth;
+    const Variant v = choose_variant(in);
     // default occupancy, measured (profiles/query_timing.txt): MODE 17 fits 7 waves per SIMD with 2 spilled
     // registers (incoherent rays 1.20 vs 1.35 ms at 5); the leaf-tree MODE 21 spills ~100 there (5.0 vs 3.9 ms)
-    const int w = p->waves_per_simd ? p->waves_per_simd : (mode == 21 ? 5 : 7);
-    return check(launch_query(stack, mode, w, q, (hipStream_t)stream), "query_kernel launch");
+    const int w = p->waves_per_simd ? p->waves_per_simd : ((v.mode & rtfast::TREE_BIT) ? 5 : 7);
+    return check(launch_query(v.stack, v.mode, w, q, (hipStream_t)stream), "query_kernel launch");
 }
 
 // 1 when librt_hip_exp.so's render paths are registered (rt_render.h ExperimentalKernels).
@@ -1189,6 +1125,27 @@ extern "C" int rt_twin_check_host(const float rec[12], const float o[3], const f
     float kd, ke;
     rt_twin_bounds(rec, &kd, &ke);
     return (rtfast::twin_rejected(d, u, v, uv, dn, kd, ke) ? 1 : 0) | (ok(d2, u2, v2, uv2) ? 2 : 0) | (ok(d, u, v, uv) ? 4 : 0);
+}
+
+// choose_variant (rt_variant.h) for tests/test_variant_cpu.py: in = {tune, stats, lane_cost, refill, has_tree, screens,
+// arrays_complete, depth, want_entry}, out = {family, mode, stack, needs_plugin, use_entry}.
+extern "C" void rt_variant_host(const int32_t in[9], int32_t out[5]) {
+    const rtk::VariantInput vi{(uint32_t)in[0], in[1] != 0, in[2] != 0, in[3] != 0, in[4] != 0,
+                               in[5] != 0, in[6] != 0, in[7], in[8] != 0};
+    const rtk::Variant v = rtk::choose_variant(vi);
+    out[0] = v.family, out[1] = v.mode, out[2] = v.stack, out[3] = v.needs_plugin, out[4] = v.use_entry;
+}
+
+// Whether the unit of `family` instantiates `mode`, from the rows its launcher is built from (rt_render.h).
+template <int... MODES>
+static bool one_of(int mode) { return ((mode == MODES) || ...); }
+extern "C" int rt_family_has_mode_host(int family, int mode) {
+    switch (family) {
+#define RT_FAMILY_CASE(FAM, NAME, STATS, ...) case rtk::FAM: return one_of<__VA_ARGS__>(mode);
+        RT_FAST_FAMILIES(RT_FAMILY_CASE)
+#undef RT_FAMILY_CASE
+    }
+    return 0;
 }
 
 extern "C" int rt_cluster_cull_host(const float origin[3], const float nd[3], float best, const float node[16]) {

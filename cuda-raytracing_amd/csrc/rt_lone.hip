@@ -111,7 +111,7 @@ __device__ __forceinline__ void lone_leaf(const RenderArgs& a, const float4* tri
     // big leaf: the wave's cooperative round for the one ray (lane 0 holds it, like every lane)
     const float4 lead = tris[3 * (size_t)f0 + 2];
     const uint32_t pf = __float_as_uint(lead.w), po = __float_as_uint(lead.z);
-    if ((MODE & 4) && pf == 2u && a.tree && a.flat) {
+    if ((MODE & rtfast::TREE_BIT) && pf == 2u && a.tree && a.flat) {
         Trav T{f0, c0, 0};
         coop_tree<false>(tris, a.tree, a.ltris, a.flat, 1ull, po, R, h, T, scratch, a.tune, c);
     } else if ((pf & 1u) && a.pairs) {  // pf 3: a screen record precedes the pairs (mirror.h)
@@ -309,9 +309,11 @@ hipError_t launch_lone(const RenderArgs& a, const int32_t* lone_slots, int lone_
     if (lone_count <= 0) return hipSuccess;
     const float4* tl = reinterpret_cast<const float4*>(treelets);
     if (a.tree)
-        hipLaunchKernelGGL(render_lone_kernel<5>, dim3(lone_count), dim3(WAVE), 0, s, a, lone_slots, lone_count, tl);
+        hipLaunchKernelGGL(render_lone_kernel<rtfast::MODE_NOSPLIT | rtfast::TREE_BIT>, dim3(lone_count), dim3(WAVE), 0, s, a,
+                           lone_slots, lone_count, tl);
     else
-        hipLaunchKernelGGL(render_lone_kernel<1>, dim3(lone_count), dim3(WAVE), 0, s, a, lone_slots, lone_count, tl);
+        hipLaunchKernelGGL(render_lone_kernel<rtfast::MODE_NOSPLIT>, dim3(lone_count), dim3(WAVE), 0, s, a, lone_slots,
+                           lone_count, tl);
     return hipGetLastError();
 }
 

@@ -3,8 +3,8 @@
 // forms the camera ray of its pixel centre), runs GetRayHit's sphere loop and rtfast::trace exactly as
 // render_fast_body does (rt_fast_body.h), and writes one 48-byte hit record with the attributes shade_segment
 // computes -- no RNG, no shading, no sky, no surface.  The variants are the ones a production frame runs at
-// RT_TUNE 0: MODE 17 (its lean form 17 | 128 when lean_mode's conditions hold) for scenes without leaf trees,
-// 21 with them; stacks of 30 / 40 / 64 entries; 5, 6 and 7 waves per SIMD.  rt_kernel.hip picks one
+// RT_TUNE 0 (rt_variant.h choose_variant): MODE_PROD = 17 or its lean form 17 | 128 for scenes without leaf
+// trees, 21 with them; stacks of 30 / 40 / 64 entries; 5, 6 and 7 waves per SIMD.  rt_kernel.hip picks one
 // (rt_trace_rays).  Compiled with the flags of every other unit (rt_fast_body.h RT_FAST_FAMILY, build.py).
 #include <hip/hip_runtime.h>
 
@@ -117,7 +117,7 @@ __device__ __forceinline__ void query_body(const QueryArgs& q,
     __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(W))) void NAME(QueryArgs q) { \
         constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL; \
         __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE]; \
-        __shared__ uint32_t scratch_lds[((MODE & 4) ? 64 : 0) + rtfast::DEFER_WORDS]; \
+        __shared__ uint32_t scratch_lds[((MODE & rtfast::TREE_BIT) ? 64 : 0) + rtfast::DEFER_WORDS]; \
         uint32_t ovf[STACK > SL ? STACK - SL : 1]; \
         query_body<STACK, MODE>(q, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds); \
     }
@@ -137,10 +137,11 @@ hipError_t launch_occ(int w, const QueryArgs& q, hipStream_t s) {
 
 template <int STACK>
 hipError_t dispatch(int mode, int w, const QueryArgs& q, hipStream_t s) {
+    using namespace rtfast;
     switch (mode) {
-        case 17: return launch_occ<STACK, 17>(w, q, s);
-        case 17 | rtfast::LEAN_BIT: return launch_occ<STACK, 17 | rtfast::LEAN_BIT>(w, q, s);
-        case 21: return launch_occ<STACK, 21>(w, q, s);
+        case MODE_PROD: return launch_occ<STACK, MODE_PROD>(w, q, s);
+        case MODE_PROD | LEAN_BIT: return launch_occ<STACK, MODE_PROD | LEAN_BIT>(w, q, s);
+        case MODE_PROD | TREE_BIT: return launch_occ<STACK, MODE_PROD | TREE_BIT>(w, q, s);
     }
     return hipErrorInvalidValue;
 }

@@ -1,20 +1,46 @@
-// rt_render.h -- launchers of the render kernels, one family per translation unit (rt_kernel.hip
-// dispatches; the families compile in parallel).  `stack` is the traversal stack size of the
-// instantiation (30, 40 or 64 entries: the scene's BVH depth + 2 rounded up), `mode` the MODE bits of
-// render_fast_body (rt_fast_body.h).  Each returns hipErrorInvalidValue for a mode it does not hold.
+// rt_render.h -- launchers of the render kernels, one family per translation unit (rt_kernel.hip chooses and
+// launches through the family table below; the families compile in parallel).  `stack` is the traversal stack
+// size of the instantiation (30, 40 or 64 entries), `mode` the MODE bits of render_fast_body (rt_fast_body.h;
+// both from rt_variant.h choose_variant).  Each returns hipErrorInvalidValue for a mode it does not hold.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "rt_common.h"
+#include "rt_variant.h"
 
 namespace rtk {
 
-// In librt_hip.so (the product): the kernels the production path launches.
-hipError_t launch_fast_prod(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);    // 17, 21
-hipError_t launch_fast_lean(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);    // 17 | 128
-hipError_t launch_fast_timing(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);  // 25, 29, 9, 25 | 128
-hipError_t launch_fast_stats(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);   // 2, 6 (counting)
+// The families of render_fast_body, one row each, in Family's order (rt_variant.h): family, launcher, STATS, the
+// MODEs its unit instantiates (the unit defines the launcher from its row: rt_fast_body.h RT_FAST_FAMILY).  The
+// first four are in librt_hip.so (the product): the kernels the production path launches.  The others are in
+// librt_hip_exp.so (rt_exp.hip): exact alternatives kept for A/B measurement and their parity tests, none of which
+// serves the benchmark -- loading the library registers them (rt_render then accepts the flags / knobs that select
+// them; without it those requests are refused).
+#define RT_FAMILY_PROD FAM_PROD, launch_fast_prod, false, rtfast::MODE_PROD, rtfast::MODE_PROD | rtfast::TREE_BIT  // 17, 21
+#define RT_FAMILY_LEAN FAM_LEAN, launch_fast_lean, false, rtfast::MODE_PROD | rtfast::LEAN_BIT                    // 17 | 128
+#define RT_FAMILY_TIMING /* 25, 29, 9, 25 | 128 */ \
+    FAM_TIMING, launch_fast_timing, false, rtfast::MODE_PROD | rtfast::TIMING_BIT, \
+    rtfast::MODE_PROD | rtfast::TIMING_BIT | rtfast::TREE_BIT, rtfast::MODE_NOSPLIT | rtfast::TIMING_BIT, \
+    rtfast::MODE_PROD | rtfast::TIMING_BIT | rtfast::LEAN_BIT
+#define RT_FAMILY_STATS FAM_STATS, launch_fast_stats, true, rtfast::BIG_SCALAR, rtfast::BIG_SCALAR | rtfast::TREE_BIT  // 2, 6
+#define RT_FAMILY_AB FAM_AB, launch_fast_ab, false, rtfast::MODE_NOSPLIT, rtfast::MODE_NOSPLIT | rtfast::TREE_BIT  // 1, 5
+#define RT_FAMILY_AB2 FAM_AB2, launch_fast_ab2, false, rtfast::BIG_SCALAR, rtfast::BIG_PAIRS                       // 2, 0
+#define RT_FAMILY_REFILL /* 81, 85 */ \
+    FAM_REFILL, launch_fast_refill, false, rtfast::MODE_PROD | rtfast::REFILL_BIT, \
+    rtfast::MODE_PROD | rtfast::REFILL_BIT | rtfast::TREE_BIT
+#define RT_FAMILY_SCREEN /* 49, 53, 57, 61 */ \
+    FAM_SCREEN, launch_fast_screen, false, rtfast::MODE_PROD | rtfast::SCREEN_BIT, \
+    rtfast::MODE_PROD | rtfast::SCREEN_BIT | rtfast::TREE_BIT, rtfast::MODE_PROD | rtfast::SCREEN_BIT | rtfast::TIMING_BIT, \
+    rtfast::MODE_PROD | rtfast::SCREEN_BIT | rtfast::TIMING_BIT | rtfast::TREE_BIT
+#define RT_APPLY(X, ...) X(__VA_ARGS__)  // X on a row (expanded first)
+#define RT_FAST_FAMILIES(X) \
+    RT_APPLY(X, RT_FAMILY_PROD) RT_APPLY(X, RT_FAMILY_LEAN) RT_APPLY(X, RT_FAMILY_TIMING) RT_APPLY(X, RT_FAMILY_STATS) \
+    RT_APPLY(X, RT_FAMILY_AB) RT_APPLY(X, RT_FAMILY_AB2) RT_APPLY(X, RT_FAMILY_REFILL) RT_APPLY(X, RT_FAMILY_SCREEN)
+typedef hipError_t (*FastLauncher)(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);
+#define RT_DECLARE_FAMILY(FAM, NAME, ...) hipError_t NAME(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);
+RT_FAST_FAMILIES(RT_DECLARE_FAMILY)
+#undef RT_DECLARE_FAMILY
 // The reference-layout tracer (flat = false) or the exact-division flat tracer (rt_ref.hip).
 hipError_t launch_ref_tracer(bool flat, const RenderArgs& a, int waves, int depth, bool stats, hipStream_t s);
 
@@ -37,31 +63,24 @@ struct QueryArgs {
     const float4 *pairs, *quads, *units, *tree, *ltris, *spairs, *flat;
     const uint32_t* face_leaf;
 };
-// mode 17, 17 | LEAN_BIT or 21; occupancy 5, 6 or 7 waves per SIMD
+// mode MODE_PROD, MODE_PROD | LEAN_BIT or MODE_PROD | TREE_BIT (17, 145, 21); occupancy 5, 6 or 7 waves per SIMD
 hipError_t launch_query(int stack, int mode, int waves_per_simd, const QueryArgs& q, hipStream_t s);
 
-// In librt_hip_exp.so (rt_exp.hip): exact alternatives kept for A/B measurement and their parity
-// tests, none of which serves the benchmark -- loading the library registers them (rt_render then
-// accepts the flags / knobs that select them; without it those requests are refused).
-hipError_t launch_fast_ab(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);      // 1, 5, 2, 0
-hipError_t launch_fast_refill(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);  // 81, 85
-hipError_t launch_fast_screen(int stack, int mode, const RenderArgs& a, int waves, hipStream_t s);  // 49, 53, 57, 61
+// In librt_hip_exp.so beside its families:
 // The lone-pixel kernel (rt_lone.hip): one wave per slot of `lone_slots`, through the treelets.
 hipError_t launch_lone(const RenderArgs& a, const int32_t* lone_slots, int lone_count, const void* treelets, hipStream_t s);
 // The wavefront tracer (rt_wavefront.hip): shade / trace launches per segment generation.
 hipError_t launch_wavefront(const RenderArgs& a, int depth, hipStream_t s);
 
 struct ExperimentalKernels {
-    decltype(&launch_fast_ab) fast_ab;
-    decltype(&launch_fast_refill) fast_refill;
+    FastLauncher fast[FAM_COUNT];  // the plugin's families; null at the product's
     decltype(&launch_lone) lone;
     decltype(&launch_wavefront) wavefront;
-    decltype(&launch_fast_screen) fast_screen;
 };
 // Layout stamp of what the plugin shares with librt_hip.so (RenderArgs by reference, this table): a
 // version bumped by hand when a field changes meaning, and the two sizes.  A plugin built against another
 // layout is refused at registration instead of reading a different struct (rt_exp_abi_version).
-constexpr uint32_t kExperimentalAbi = (2u << 24) ^ ((uint32_t)sizeof(RenderArgs) << 8) ^ (uint32_t)sizeof(ExperimentalKernels);
+constexpr uint32_t kExperimentalAbi = (3u << 24) ^ ((uint32_t)sizeof(RenderArgs) << 8) ^ (uint32_t)sizeof(ExperimentalKernels);
 // rt_kernel.hip: the registered table (nullptr until librt_hip_exp.so is loaded); a table whose `abi` is
 // not this library's kExperimentalAbi is refused (rt_last_error says so, rt_experimental_loaded stays 0).
 void register_experimental_kernels(const ExperimentalKernels* k, uint32_t abi);

@@ -253,7 +253,7 @@ __device__ __forceinline__ void wf_trace_body(const RenderArgs& a, const WfBuf& 
     const uint32_t root_first = __float_as_uint(root_hi.z), root_count = __float_as_uint(root_hi.w);
     constexpr int SL = STACK < 16 ? STACK : 16;
     __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE];
-    __shared__ uint32_t scratch_lds[(MODE & 4) ? 64 : 1];
+    __shared__ uint32_t scratch_lds[(MODE & rtfast::TREE_BIT) ? 64 : 1];
     uint32_t ovf[STACK > SL ? STACK - SL : 1];
     const rtfast::Stack<SL> stk{stack_lds, ovf};
     const float4* nodes4 = reinterpret_cast<const float4*>(a.nodes);
@@ -379,10 +379,11 @@ hipError_t wf_buffers(long long P, int W, int gens, hipStream_t s, WfBuf* out) {
     return hipSuccess;
 }
 
+constexpr int WF_PLAIN = rtfast::MODE_PROD, WF_TREE = rtfast::MODE_PROD | rtfast::TREE_BIT;  // 17, 21: big_round's modes
 template <int STACK>
 hipError_t wf_launch_trace(const RenderArgs& a, const WfBuf& b, int g, hipStream_t s) {
-    if (a.tree) hipLaunchKernelGGL((wf_trace_kernel<STACK, 21>), dim3(b.W), dim3(WAVE), 0, s, a, b, g);
-    else hipLaunchKernelGGL((wf_trace_kernel<STACK, 17>), dim3(b.W), dim3(WAVE), 0, s, a, b, g);
+    if (a.tree) hipLaunchKernelGGL((wf_trace_kernel<STACK, WF_TREE>), dim3(b.W), dim3(WAVE), 0, s, a, b, g);
+    else hipLaunchKernelGGL((wf_trace_kernel<STACK, WF_PLAIN>), dim3(b.W), dim3(WAVE), 0, s, a, b, g);
     return hipGetLastError();
 }
 
@@ -392,11 +393,11 @@ hipError_t launch_wavefront(const RenderArgs& a, int depth, hipStream_t s) {
     const long long P = a.entry_count;
     if (P <= 0 || P > (1ll << 31)) return hipErrorInvalidValue;
     const int gens = a.spp * a.bounces;  // segments per pixel at most: spp x bounces
-    const int stack = (depth >= 0 && depth + 2 <= 30) ? 30 : (depth >= 0 && depth + 2 <= 40) ? 40 : 64;
+    const int stack = variant_stack(depth);
     // regions = the trace launch's resident waves, so every region's trace wave runs at once
-    int W = stack == 30 ? resident_waves(a.tree ? wf_trace_kernel<30, 21> : wf_trace_kernel<30, 17>)
-                  : stack == 40 ? resident_waves(a.tree ? wf_trace_kernel<40, 21> : wf_trace_kernel<40, 17>)
-                                : resident_waves(a.tree ? wf_trace_kernel<64, 21> : wf_trace_kernel<64, 17>);
+    int W = stack == 30 ? resident_waves(a.tree ? wf_trace_kernel<30, WF_TREE> : wf_trace_kernel<30, WF_PLAIN>)
+                  : stack == 40 ? resident_waves(a.tree ? wf_trace_kernel<40, WF_TREE> : wf_trace_kernel<40, WF_PLAIN>)
+                                : resident_waves(a.tree ? wf_trace_kernel<64, WF_TREE> : wf_trace_kernel<64, WF_PLAIN>);
     if (W <= 0) return hipErrorInvalidValue;
     // RT_TUNE bits 16-17: regions = 2^v x the resident waves (the dispatcher then balances the
     // regions over the waves as they finish; measured 29.4 / 29.9 / 31.6 / 32.4 ms for v = 0-3)

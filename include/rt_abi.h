@@ -652,6 +652,12 @@ int rt_cluster_cull_host(const float origin[3], const float nd[3], float best, c
    the twin of triangle record `rec` (v0, e2, e1) is proven rejected from rec's own glm values for the
    ray (origin, nd), bit 1 the twin passes glm's predicate, bit 2 rec does.  For tests. */
 int rt_twin_check_host(const float rec[12], const float origin[3], const float nd[3]);
+/* The render kernel variant rt_render chooses for a frame (csrc/rt_variant.h choose_variant), on the host and
+   without a GPU: in = {tune, stats, lane_cost, refill, has_tree, screens, arrays_complete, depth, want_entry},
+   out = {family, mode, stack, needs_plugin, use_entry}.  rt_family_has_mode_host: 1 when the translation unit
+   of `family` instantiates `mode` (csrc/rt_render.h, the family table).  For tests. */
+void rt_variant_host(const int32_t in[9], int32_t out[5]);
+int rt_family_has_mode_host(int family, int mode);
 /* The traversal's private node array (mirror.h nodes: GPUBVHNode records, sibling pairs 64-B
    aligned in right-first pre-order), built on the host: *count receives the node count; nodes (may
    be NULL) receives the records.  0 or -1 with rt_last_error(). */

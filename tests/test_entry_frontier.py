@@ -7,7 +7,7 @@ whose box contains its children's, and the record's nodes together with the node
 once.  Replay, for sampled sub-tiles (all of them at 64x36), per pixel the four jitter corners and 8 random
 jitters: the same face and the same distance bits from the root and from the record, no node left out passes
 IntersectAABB with len = +inf, and the stack the kernel's walk holds from the record stays inside the stack
-rt_kernel.hip launch_fast picks for a frame with a table.
+rt_variant.h choose_variant picks for a frame with a table.
 """
 import numpy as np
 import pytest
@@ -146,7 +146,7 @@ def check_replay(c, tiles, seed):
     assert np.array_equal(r["t_root"].view(np.uint32), r["t_entry"].view(np.uint32))
     assert (r["face_root"] != 0xffffffff).any()
     # Stack depth.  The root walk holds at most one pending sibling per level; from the record the lane starts with
-    # up to K entries, so under a record node it can hold (K - 1) more.  launch_fast's choice, restated: the stack
+    # up to K entries, so under a record node it can hold (K - 1) more.  choose_variant's choice (rt_variant.h), restated: the stack
     # instantiation for depth + 2 + (K - 1).
     depth = c.scene.max_depth()
     assert int(r["stack_root"].max()) <= depth + 1

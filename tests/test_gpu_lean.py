@@ -1,6 +1,6 @@
 """The fixed-policy ("lean") production kernel (rt_fast_lean.hip, MODE 17 | 128): a frame that sets no RT_TUNE
 knob the kernel reads, on a scene without leaf trees whose mirror holds every array, renders through it
-(rt_kernel.hip launch_fast).  Every case is a 64x36 frame, 4 spp, 6 bounces, at 5, 6 and 7 waves per SIMD,
+(rt_variant.h choose_variant).  Every case is a 64x36 frame, 4 spp, 6 bounces, at 5, 6 and 7 waves per SIMD,
 surface and final RNG states compared bit for bit.
 
 The reference is the CPU oracle (rt_testlib) wherever it can build the scene: the bunny, the 4-bunny
