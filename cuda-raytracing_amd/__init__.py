@@ -101,6 +101,20 @@ class TraceParams(ctypes.Structure):
                 ("hits", ctypes.c_void_p), ("flags", ctypes.c_uint32), ("waves_per_simd", ctypes.c_int32)]
 
 
+class OcclusionParams(ctypes.Structure):
+    """rt_occlusion_params (rt_abi.h)."""
+    _fields_ = [("rays", ctypes.c_void_p), ("count", ctypes.c_int64), ("occluded", ctypes.c_void_p),
+                ("flags", ctypes.c_uint32), ("waves_per_simd", ctypes.c_int32)]
+
+
+class AoParams(ctypes.Structure):
+    """rt_ao_params (rt_abi.h)."""
+    _fields_ = [("hits", ctypes.c_void_p), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("directions", ctypes.c_void_p), ("direction_count", ctypes.c_int32), ("samples", ctypes.c_int32),
+                ("radius", ctypes.c_float), ("bias", ctypes.c_float), ("ao", ctypes.c_void_p), ("scratch", ctypes.c_void_p),
+                ("scratch_bytes", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("waves_per_simd", ctypes.c_int32)]
+
+
 class DenoiseParams(ctypes.Structure):
     """rt_denoise_params (rt_abi.h)."""
     _fields_ = [("surface", ctypes.c_void_p), ("pitch", ctypes.c_uint64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
@@ -118,7 +132,7 @@ DENOISE_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_plane": 0.03
 
 assert ctypes.sizeof(GPUScene) == 136 and ctypes.sizeof(GPUMaterial) == 64
 assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(Hit) == 48 and ctypes.sizeof(TraceParams) == 40
-assert ctypes.sizeof(DenoiseParams) == 96
+assert ctypes.sizeof(DenoiseParams) == 96 and ctypes.sizeof(OcclusionParams) == 32 and ctypes.sizeof(AoParams) == 72
 
 # name -> (restype, argtypes); every symbol include/rt_abi.h declares.
 _P, _I, _U32, _U64, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_size_t
@@ -128,6 +142,9 @@ SIGNATURES = {
     "init_rng": (None, [_U32, _U32, _P, ctypes.c_uint]),
     "rt_render": (_I, [ctypes.POINTER(RenderParams), _P, _P]),
     "rt_trace_rays": (_I, [ctypes.POINTER(TraceParams), _P, _P]),
+    "rt_occluded": (_I, [ctypes.POINTER(OcclusionParams), _P, _P]),
+    "rt_ao_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "rt_ao": (_I, [ctypes.POINTER(AoParams), _P, _P]),
     "rt_denoise_scratch_bytes": (_SZ, [_I, _I]),
     "rt_denoise": (_I, [ctypes.POINTER(DenoiseParams), _P]),
     "rt_foreign_mirror_wait": (_I, [_P]),
@@ -585,6 +602,97 @@ def gbuffer(scene, width, height, stream=None, waves_per_simd=0):
             "kind": f["kind"].reshape(h, w).clone()}
 
 
+def occluded(scene, rays, out=None, stream=None, waves_per_simd=0):
+    """rt_occluded: whether each ray of a float32 CUDA tensor [N, 8] (rt_ray rows, as trace_rays takes them) hits
+    anything before its tmax, as a uint8 tensor [N] (`out`, or a new one): byte i is `kind != 0` of the record
+    trace_rays gives for ray i, for every ray, at a fraction of the cost where the traversal may stop at the first
+    occluder.  Stream-ordered on `stream` (default: torch's current stream)."""
+    assert rays.dtype == torch.float32 and rays.is_cuda and rays.is_contiguous() and rays.dim() == 2 and rays.shape[1] == 8
+    n = rays.shape[0]
+    if out is None:
+        with _allocating_on(stream):
+            out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+    assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.dim() == 1 and out.shape[0] >= n
+    if n == 0:  # rt_occluded returns at once for count 0; an empty tensor has no address to pass
+        return out
+    p = OcclusionParams()
+    p.rays, p.count, p.occluded = rays.data_ptr(), n, out.data_ptr()
+    p.waves_per_simd = int(waves_per_simd)
+    gpu = scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene)
+    _check(lib().rt_occluded(ctypes.byref(p), ctypes.cast(gpu, ctypes.c_void_p), _stream_ptr(stream)), "rt_occluded")
+    return out
+
+
+def ao_directions(count=256):
+    """A [count, 4] float32 table of unit vectors for ambient_occlusion (w = 0): the Fibonacci sphere points
+    z = 1 - (2k + 1) / count, azimuth k * pi * (3 - sqrt(5)), computed in float64 and rounded."""
+    k = np.arange(int(count), dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / float(count)
+    r = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    out = np.zeros((int(count), 4), dtype=np.float32)
+    out[:, 0], out[:, 1], out[:, 2] = r * np.cos(phi), r * np.sin(phi), z
+    return out
+
+
+_ao_default_tables = {}  # device -> ao_directions(256) on it
+
+
+def _ao_default_directions(device):
+    """ao_directions(256) on `device`, built and uploaded once per device (a synchronous copy from pageable host
+    memory: complete when it returns, so the table is safe to read on any stream)."""
+    key = torch.device(device)
+    if key.type == "cuda" and key.index is None:
+        key = torch.device("cuda", torch.cuda.current_device())
+    t = _ao_default_tables.get(key)
+    if t is None:
+        t = _ao_default_tables[key] = torch.from_numpy(ao_directions(256)).to(key)
+    return t
+
+
+def ao_scratch_bytes(width, height, samples):
+    """rt_ao_scratch_bytes: bytes of scratch rt_ao needs."""
+    return int(lib().rt_ao_scratch_bytes(int(width), int(height), int(samples)))
+
+
+def ambient_occlusion(scene, hits, width, height, radius, samples=8, bias=0.001, directions=None, out=None, scratch=None,
+                      stream=None, waves_per_simd=0):
+    """rt_ao: the ambient-occlusion image [H, W] float32 (1 = open, 0 = closed; 1 where the camera ray missed) of an
+    uploaded Scene from the first-hit records `hits` (float32 [H*W, 12], what trace_camera returns): per pixel,
+    `samples` cosine-weighted rays of length `radius` from the hit point, offset along its normal by `bias` times the
+    hit distance.  `directions`: a float32 [K, 4] table of unit vectors; default ao_directions(256), uploaded once
+    per device and kept.  Stream-ordered on `stream` (default: torch's current stream) when `directions` is a CUDA
+    tensor or the default; a numpy table is uploaded by this call with a synchronous copy.  What is allocated here
+    is allocated on that stream."""
+    w, h = int(width), int(height)
+    assert hits.dtype == torch.float32 and hits.is_cuda and hits.is_contiguous() and hits.dim() == 2
+    assert hits.shape[1] == 12 and hits.shape[0] >= w * h
+    need = ao_scratch_bytes(w, h, samples)
+    with _allocating_on(stream):
+        if directions is None:
+            directions = _ao_default_directions(hits.device)
+        if not isinstance(directions, torch.Tensor):
+            directions = torch.from_numpy(np.ascontiguousarray(directions, dtype=np.float32)).to(hits.device)
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.float32, device=hits.device)
+        if scratch is None and need:
+            scratch = torch.empty((need,), dtype=torch.uint8, device=hits.device)
+    assert directions.dtype == torch.float32 and directions.is_cuda and directions.is_contiguous()
+    assert directions.dim() == 2 and directions.shape[1] == 4
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.numel() >= w * h
+    p = AoParams()
+    p.hits, p.width, p.height = hits.data_ptr(), w, h
+    p.directions, p.direction_count, p.samples = directions.data_ptr(), directions.shape[0], int(samples)
+    p.radius, p.bias, p.ao = float(radius), float(bias), out.data_ptr()
+    if scratch is not None:
+        assert scratch.is_cuda and scratch.is_contiguous()
+        p.scratch, p.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
+    p.waves_per_simd = int(waves_per_simd)
+    gpu = scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene)
+    _check(lib().rt_ao(ctypes.byref(p), ctypes.cast(gpu, ctypes.c_void_p), _stream_ptr(stream)), "rt_ao")
+    return out
+
+
 def denoise_scratch_bytes(width, height):
     """rt_denoise_scratch_bytes: bytes of scratch rt_denoise needs for a width x height frame."""
     return int(lib().rt_denoise_scratch_bytes(int(width), int(height)))
@@ -894,6 +1002,19 @@ class RayTracer:
         self.scene.set_viewport(self.width, self.height)
         self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
         return denoise(self.scene, self.surface, self.width, self.height, **kw)
+
+    def ao(self, radius, **kw):
+        """The ambient-occlusion image [H, W] of the current camera and size (module-level ambient_occlusion();
+        **kw are its samples, bias, directions, hits, stream, ...).  Uploads the scene like process(); the frame
+        index, the surfaces and the RNG states are left alone."""
+        self.scene.set_viewport(self.width, self.height)
+        self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
+        stream = kw.get("stream")
+        hits = kw.pop("hits", None)
+        if hits is None:
+            with _allocating_on(stream):
+                hits = trace_camera(self.scene, self.width, self.height, stream=stream)
+        return ambient_occlusion(self.scene, hits, self.width, self.height, radius, **kw)
 
     def save(self, path):
         """The current frame: ``.pfm`` linear RGB, ``.ppm`` as the reference's viewer shows it

@@ -1153,6 +1153,22 @@ __device__ __forceinline__ bool defer_leaf(uint32_t* D, const float4* nodes4, co
     return true;
 }
 
+// Any-hit queries (trace<.., ANY>, rt_occlude.hip): whether a lane may stop at its first accept.  defer_leaf's
+// gate, restated for the distance the lane enters with: inside it every product of the slab and triangle
+// tests is finite (vertices lie in the root box, |det| > eps bounds 1 / det), so no accepted distance is NaN,
+// every accept lies below `closest`, and "something is accepted" does not depend on the order of the walk.
+__device__ __forceinline__ bool any_gate(const float4* nodes4, const Ray& R, float closest) {
+    if (!(closest <= 1e30f) || !R.fast) return false;
+    const f4v lo = ((ConstF4)nodes4)[0], hi = ((ConstF4)nodes4)[1];
+    const float sc = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(lo.w))),
+                           fmaxf(fabsf(hi.x), fabsf(hi.y)));
+    const float ro = fmaxf(fmaxf(fabsf(R.o.x), fabsf(R.o.y)), fabsf(R.o.z));
+    return sc < 0x1p16f && ro < 0x1p16f;
+}
+
+// What a closest-hit instantiation holds and passes in place of an any-hit lane's `first_ends` (trace): nothing.
+struct AnyOff {};
+
 // pop, then: a big leaf popped as the lane's first is deferred (defer_leaf) and popping goes on
 template <bool DEFER, class S>
 __device__ __forceinline__ bool pop_d(const float4* nodes4, uint32_t* D, const S& stk, const Ray& R, const Hit& h, Trav& T) {
@@ -1357,9 +1373,9 @@ __device__ __forceinline__ bool big_round_d(const float4* nodes4, uint32_t* D, c
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t bcastu(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
 
-template <class S>
+template <bool ANY = false, class S, class F = AnyOff>
 __device__ __forceinline__ void lone_traverse(const float4* nodes4, const float4* tris, const S& stk, int r,
-                                              const Ray& R, Hit& h, Trav& T, bool& active) {
+                                              const Ray& R, Hit& h, Trav& T, bool& active, F first_ends = {}) {
     constexpr int SL = S::LDS_ENTRIES;
     const int lane = (int)(threadIdx.x & 63u);
     const int sp0 = (int)bcastu((uint32_t)T.sp, r);
@@ -1469,6 +1485,13 @@ __device__ __forceinline__ void lone_traverse(const float4* nodes4, const float4
                 best = bcast(t, wl), bx = bcast(x, wl), by = bcast(y, wl), kind = 2;
                 id = __float_as_uint(tris[3 * (cf + mi) + 2].y);
             }
+            if constexpr (ANY) {  // any-hit (trace): a lone ray that stops at its first accept leaves here, not at the next pop
+                if (kind != 0 && __builtin_amdgcn_readlane(first_ends ? 1 : 0, r) != 0) {
+                    done = true;
+                    sp = 0;
+                    break;
+                }
+            }
             do_pop = true;
         } else {
             break;  // a big leaf: the wave's big-leaf round takes over
@@ -1521,7 +1544,15 @@ __device__ __forceinline__ void lone_traverse(const float4* nodes4, const float4
 // reference's triangle tests plus the tree's own work).  The bits' names: rt_variant.h.
 // ENTRY (the lean render kernels): a lane whose `erec` is not ENTRY_NONE starts from record `erec` of the entry
 // table `etab` (trav_begin_entry) instead of the root.
-template <bool STATS, int MODE, bool ENTRY = false, class S, class C>
+// ANY (the occlusion kernels, rt_occlude.hip): a lane that enters without a hit and inside any_gate is done at
+// its first accept -- h.kind != 0 is then its whole answer, h's other fields are those of some accepted
+// primitive, not the closest.  Until nothing has been accepted `closest` is the distance the lane entered with,
+// and the slab test (tmin < closest), the leaf-tree cull and the accept (0 <= t < closest) are monotone in it,
+// so a first accept exists in this walk exactly when the reference's walk accepts something.  Every other lane
+// (outside the gate, or entering with a sphere's hit) runs the closest-hit traversal unchanged.  A finished lane
+// stays in the wave's loop as a lane that is not active: the big-leaf rounds and the lone traversal are
+// wave-cooperative.  No deferral: which hit wins is irrelevant here.
+template <bool STATS, int MODE, bool ENTRY = false, bool ANY = false, class S, class C>
 __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, const float4* pairs,
                                       const float4* tree, const float4* ltris, const float4* flat,
                                       const float4* spairs, uint32_t tune_arg, const S& stk, uint32_t* scratch,
@@ -1544,7 +1575,12 @@ __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, 
     // deferred big leaves (defer_leaf): production, timing and refill variants, not the screen ones; D = this
     // lane's words, or null when deferral is off (RT_TUNE bit 24).  Only the leaf-tree kernels defer: config 2's
     // 7-wave kernel spills 53 -> 186 dwords with the deferral compiled in.
-    constexpr bool DEFER = !STATS && (MODE & SCREEN_BIT) == 0 && (MODE & TREE_BIT) != 0;
+    constexpr bool DEFER = !ANY && !STATS && (MODE & SCREEN_BIT) == 0 && (MODE & TREE_BIT) != 0;
+    // ANY: whether this lane stops at its first accept (a bool); otherwise an empty AnyOff -- no state, no argument
+    const auto first_ends = [&] {
+        if constexpr (ANY) return h.kind == 0 && any_gate(nodes4, R, h.best);
+        else return AnyOff{};
+    }();
     uint32_t* const D = (DEFER && (tune & (1u << 24)) == 0) ? defer_words<MODE>(scratch) : nullptr;
     if (D) D[0] = DEFER_NONE;
     unsigned long long t0 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
@@ -1574,7 +1610,8 @@ __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, 
 #ifdef RT_LANE_HIST  // diagnostic build (tools/lane_hist.sh): wave cycles of the lone-lane tails
                             const unsigned long long tl0 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
 #endif
-                            lone_traverse(nodes4, tris, stk, r, R, h, T, active);
+                            lone_traverse<ANY>(nodes4, tris, stk, r, R, h, T, active, first_ends);
+                            if constexpr (ANY) active = active && !(first_ends && h.kind != 0);
 #ifdef RT_LANE_HIST
                             if (TIMING) c.cy_ttri += __builtin_amdgcn_s_memtime() - tl0;
 #endif
@@ -1591,10 +1628,12 @@ __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, 
                 if (!mI || nL * 4u >= nI * (q + 1u)) {
                     if (leafs) {
                         active = small_step<STATS, scr_on, false, LEAN>(nodes4, tris, spairs, stk, R, h, T, c, pairs);
+                        if constexpr (ANY) active = active && !(first_ends && h.kind != 0);
                         if (TIMING) c.lane_work++;
                     }
                 } else if (inner) {
                     active = small_step<STATS, false, DEFER, LEAN>(nodes4, tris, spairs, stk, R, h, T, c, nullptr, D);
+                    if constexpr (ANY) active = active && !(first_ends && h.kind != 0);
                     if (TIMING) c.lane_work++;
                 }
 #ifdef RT_LANE_HIST
@@ -1621,6 +1660,7 @@ __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, 
             }
             if (small) {
                 active = small_step<STATS>(nodes4, tris, spairs, stk, R, h, T, c);
+                if constexpr (ANY) active = active && !(first_ends && h.kind != 0);
                 if (TIMING) c.lane_work++;
             }
             continue;
@@ -1694,6 +1734,7 @@ __device__ __forceinline__ void trace(const float4* nodes4, const float4* tris, 
             if (TIMING) c.lane_work += 3;
             if constexpr (scr_on) T.sp &= ~SCREENED;
             active = pop_d<DEFER>(nodes4, D, stk, R, h, T);
+            if constexpr (ANY) active = active && !(first_ends && h.kind != 0);
         }
         if (TIMING) {
             const unsigned long long t1 = __builtin_amdgcn_s_memtime();

@@ -14,6 +14,7 @@
 // matches the CPU oracle bit for bit ("Parity").
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -933,6 +934,39 @@ void rt_internal_forget_entry_table(const void* mirror_nodes) {
     g_entry.erase(it);
 }
 
+// The scene half of a query launch, for rt_trace_rays, rt_occluded and rt_ao (`who` names the call in the
+// messages): scenes uploaded by rt_scene_upload only; the mirror arrays a render launch passes to trace; the
+// variant a production frame of this scene runs at RT_TUNE 0 (choose_variant).
+static int query_scene(const char* who, const GPUScene* scene, QueryArgs* out, Variant* variant) {
+    const std::string w(who);
+    MirrorDevice mir;
+    if (!rt_internal_lookup_mirror(scene, &mir) || !mir.owned)
+        return set_error(w + ": this GPUScene was not uploaded by rt_scene_upload (a foreign scene has no private "
+                             "mirror to query; foreign scenes are not supported here)");
+    if (!mir.nodes || !mir.tris) return set_error(w + ": the scene's mirror has no triangles to traverse");
+    if (scene->sphere_count > 0 && !scene->gpu_spheres) return set_error(w + ": sphere_count without spheres");
+    QueryArgs q;
+    std::memset(&q, 0, sizeof(q));
+    q.width = q.height = 1;
+    q.cam = scene->camera;
+    q.spheres = scene->gpu_spheres;
+    q.sphere_count = scene->sphere_count;
+    q.scene_fast = mir.fast ? 1 : 0;
+    q.faces = scene->gpu_faces;
+    q.vertices = scene->gpu_vertices;
+    q.nodes = (const GPUBVHNode*)mir.nodes;
+    q.tris = (const FlatTri*)mir.tris;
+    q.pairs = (const float4*)mir.pairs, q.quads = (const float4*)mir.quads, q.units = (const float4*)mir.units;
+    q.tree = (const float4*)mir.tree, q.ltris = (const float4*)mir.ltris, q.spairs = (const float4*)mir.spairs;
+    q.flat = (const float4*)mir.flat;
+    q.face_leaf = (const uint32_t*)mir.face_leaf;
+    VariantInput in{};  // tune 0, no statistics / lane_cost / refill / screens / entry records
+    in.has_tree = q.tree != nullptr, in.arrays_complete = q.spairs && q.pairs && q.quads && q.units, in.depth = mir.depth;
+    *variant = choose_variant(in);
+    *out = q;
+    return 0;
+}
+
 // Ray queries (rt_abi.h): argument checks, then the query kernel (rt_query.hip) in the variant a production
 // frame of this scene runs at RT_TUNE 0 (choose_variant).  Stream-ordered: no
 // synchronisation, no allocation.
@@ -951,41 +985,94 @@ extern "C" int rt_trace_rays(const rt_trace_params* p, const GPUScene* scene, vo
     if ((((uintptr_t)p->rays) | ((uintptr_t)p->hits)) & 15u) return set_error("rt_trace_rays: rays and hits must be 16-byte aligned");
     if (count == 0) return 0;
 
-    MirrorDevice mir;
-    if (!rt_internal_lookup_mirror(scene, &mir) || !mir.owned)
-        return set_error("rt_trace_rays: this GPUScene was not uploaded by rt_scene_upload (a foreign scene has no private "
-                         "mirror to query; foreign scenes are not supported here)");
-    if (!mir.nodes || !mir.tris) return set_error("rt_trace_rays: the scene's mirror has no triangles to traverse");
-    if (scene->sphere_count > 0 && !scene->gpu_spheres) return set_error("rt_trace_rays: sphere_count without spheres");
+    QueryArgs q;
+    Variant v;
+    if (query_scene("rt_trace_rays", scene, &q, &v) != 0) return 1;
     // a short buffer would fault the GPU
     if (!camera && bytes_from(p->rays) < (size_t)count * sizeof(rt_ray)) return set_error("rt_trace_rays: rays too small");
     if (bytes_from(p->hits) < (size_t)count * sizeof(rt_hit)) return set_error("rt_trace_rays: hits too small");
-
-    QueryArgs q;
-    std::memset(&q, 0, sizeof(q));
     q.rays = p->rays;
     q.hits = p->hits;
     q.count = count;
     q.width = camera ? p->width : 1, q.height = camera ? p->height : 1;
-    q.cam = scene->camera;
-    q.spheres = scene->gpu_spheres;
-    q.sphere_count = scene->sphere_count;
-    q.scene_fast = mir.fast ? 1 : 0;
-    q.faces = scene->gpu_faces;
-    q.vertices = scene->gpu_vertices;
-    q.nodes = (const GPUBVHNode*)mir.nodes;
-    q.tris = (const FlatTri*)mir.tris;
-    q.pairs = (const float4*)mir.pairs, q.quads = (const float4*)mir.quads, q.units = (const float4*)mir.units;
-    q.tree = (const float4*)mir.tree, q.ltris = (const float4*)mir.ltris, q.spairs = (const float4*)mir.spairs;
-    q.flat = (const float4*)mir.flat;
-    q.face_leaf = (const uint32_t*)mir.face_leaf;
-    VariantInput in{};  // tune 0, no statistics / lane_cost / refill / screens / entry records
-    in.has_tree = q.tree != nullptr, in.arrays_complete = q.spairs && q.pairs && q.quads && q.units, in.depth = mir.depth;
-    const Variant v = choose_variant(in);
     // default occupancy, measured (profiles/query_timing.txt): MODE 17 fits 7 waves per SIMD with 2 spilled
     // registers (incoherent rays 1.20 vs 1.35 ms at 5); the leaf-tree MODE 21 spills ~100 there (5.0 vs 3.9 ms)
     const int w = p->waves_per_simd ? p->waves_per_simd : ((v.mode & rtfast::TREE_BIT) ? 5 : 7);
     return check(launch_query(v.stack, v.mode, w, q, (hipStream_t)stream), "query_kernel launch");
+}
+
+// Occlusion queries (rt_abi.h): the checks that need no device first, then the scene's and the buffers', then
+// the any-hit kernel (rt_occlude.hip) in rt_trace_rays' variant.  Stream-ordered: no synchronisation, no allocation.
+// Default occupancy, measured (profiles/occlusion_timing.txt): MODE 17 at 7 waves per SIMD as the query kernel
+// (incoherent rays 0.867 vs 0.874 / 0.929 ms at 6 / 5; rt_ao 2.92 vs 2.96 / 3.07 ms); the leaf-tree MODE 21 at 6, not the
+// query kernel's 5 -- without the deferral it spills 10 registers there, not 89, and is the fastest on every batch
+// (incoherent rays 4.28 vs 4.57 / 4.86 ms at 5 / 7; rt_ao 25.6 vs 26.9 / 27.5 ms).
+static int any_default_waves(const Variant& v) { return (v.mode & rtfast::TREE_BIT) ? 6 : 7; }
+
+extern "C" int rt_occluded(const rt_occlusion_params* p, const GPUScene* scene, void* stream) {
+    if (!p) return set_error("rt_occluded: null params");
+    if (!scene) return set_error("rt_occluded: null scene");
+    if (!p->occluded) return set_error("rt_occluded: null occluded");
+    if (!p->rays) return set_error("rt_occluded: null rays (there is no camera mode)");
+    if (p->flags != 0) return set_error("rt_occluded: flags must be 0");
+    if (p->waves_per_simd != 0 && (p->waves_per_simd < 5 || p->waves_per_simd > 7))
+        return set_error("rt_occluded: waves_per_simd must be 0 (default), 5, 6 or 7");
+    if (p->count < 0) return set_error("rt_occluded: negative count");
+    if (p->count > (int64_t)1 << 31) return set_error("rt_occluded: more than 2^31 rays in one call");
+    if (((uintptr_t)p->rays) & 15u) return set_error("rt_occluded: rays must be 16-byte aligned");
+    if (p->count == 0) return 0;
+
+    OcclusionArgs a;
+    Variant v;
+    if (query_scene("rt_occluded", scene, &a.q, &v) != 0) return 1;
+    // a short buffer would fault the GPU
+    if (bytes_from(p->rays) < (size_t)p->count * sizeof(rt_ray)) return set_error("rt_occluded: rays too small");
+    if (bytes_from(p->occluded) < (size_t)p->count) return set_error("rt_occluded: occluded too small");
+    a.q.rays = p->rays;
+    a.q.count = p->count;
+    a.occluded = p->occluded;
+    const int w = p->waves_per_simd ? p->waves_per_simd : any_default_waves(v);
+    return check(launch_occlusion(v.stack, v.mode, w, a, (hipStream_t)stream), "occlusion_kernel launch");
+}
+
+// The fused AO kernel keeps its samples in registers: no scratch.
+extern "C" size_t rt_ao_scratch_bytes(int, int, int) { return 0; }
+
+extern "C" int rt_ao(const rt_ao_params* p, const GPUScene* scene, void* stream) {
+    if (!p) return set_error("rt_ao: null params");
+    if (!scene) return set_error("rt_ao: null scene");
+    if (!p->hits) return set_error("rt_ao: null hits");
+    if (!p->directions) return set_error("rt_ao: null directions");
+    if (!p->ao) return set_error("rt_ao: null ao");
+    if (p->flags != 0) return set_error("rt_ao: flags must be 0");
+    if (p->waves_per_simd != 0 && (p->waves_per_simd < 5 || p->waves_per_simd > 7))
+        return set_error("rt_ao: waves_per_simd must be 0 (default), 5, 6 or 7");
+    if (p->width <= 0 || p->height <= 0) return set_error("rt_ao: width and height must be > 0");
+    const int64_t count = (int64_t)p->width * p->height;
+    if (count > (int64_t)1 << 30) return set_error("rt_ao: more than 2^30 pixels");
+    if (p->direction_count < 1 || p->direction_count > 65536) return set_error("rt_ao: direction_count must be 1..65536");
+    if (p->samples < 1 || p->samples > 64) return set_error("rt_ao: samples must be 1..64");
+    if (!(p->radius > 0.0f)) return set_error("rt_ao: radius must be > 0 and not NaN");
+    if (!(p->bias >= 0.0f) || !(p->bias <= FLT_MAX)) return set_error("rt_ao: bias must be >= 0 and finite");
+    if ((((uintptr_t)p->hits) | ((uintptr_t)p->directions)) & 15u) return set_error("rt_ao: hits and directions must be 16-byte aligned");
+    if (((uintptr_t)p->ao) & 3u) return set_error("rt_ao: ao must be 4-byte aligned");
+    const size_t need = rt_ao_scratch_bytes(p->width, p->height, p->samples);
+    if (need && (!p->scratch || p->scratch_bytes < need)) return set_error("rt_ao: scratch too small (rt_ao_scratch_bytes)");
+
+    AoArgs a;
+    Variant v;
+    if (query_scene("rt_ao", scene, &a.q, &v) != 0) return 1;
+    if (bytes_from(p->hits) < (size_t)count * sizeof(rt_hit)) return set_error("rt_ao: hits too small");
+    if (bytes_from(p->directions) < (size_t)p->direction_count * 16) return set_error("rt_ao: directions too small");
+    if (bytes_from(p->ao) < (size_t)count * 4) return set_error("rt_ao: ao too small");
+    a.q.hits = const_cast<rt_hit*>(p->hits);  // read only (rt_render.h AoArgs)
+    a.q.count = count;
+    a.directions = (const float4*)p->directions;
+    a.direction_count = p->direction_count, a.samples = p->samples;
+    a.radius = p->radius, a.bias = p->bias;
+    a.ao = p->ao;
+    const int w = p->waves_per_simd ? p->waves_per_simd : any_default_waves(v);
+    return check(launch_ao(v.stack, v.mode, w, a, (hipStream_t)stream), "ao_kernel launch");
 }
 
 // 1 when librt_hip_exp.so's render paths are registered (rt_render.h ExperimentalKernels).

@@ -66,6 +66,23 @@ struct QueryArgs {
 // mode MODE_PROD, MODE_PROD | LEAN_BIT or MODE_PROD | TREE_BIT (17, 145, 21); occupancy 5, 6 or 7 waves per SIMD
 hipError_t launch_query(int stack, int mode, int waves_per_simd, const QueryArgs& q, hipStream_t s);
 
+// The any-hit kernels (rt_occlude.hip, rt_occluded / rt_ao): the query kernel's variants through trace<.., ANY>.
+// `q` carries the scene and the launch size: for rt_occluded its rays and count (hits, width, height, cam, faces and
+// vertices unused); for rt_ao the first-hit records in `hits` (read only) and count = width * height pixels.
+struct OcclusionArgs {
+    QueryArgs q;
+    uint8_t* occluded;  // count bytes
+};
+struct AoArgs {
+    QueryArgs q;
+    const float4* directions;
+    int direction_count, samples;
+    float radius, bias;
+    float* ao;  // count floats
+};
+hipError_t launch_occlusion(int stack, int mode, int waves_per_simd, const OcclusionArgs& a, hipStream_t s);
+hipError_t launch_ao(int stack, int mode, int waves_per_simd, const AoArgs& a, hipStream_t s);
+
 // In librt_hip_exp.so beside its families:
 // The lone-pixel kernel (rt_lone.hip): one wave per slot of `lone_slots`, through the treelets.
 hipError_t launch_lone(const RenderArgs& a, const int32_t* lone_slots, int lone_count, const void* treelets, hipStream_t s);

@@ -357,6 +357,101 @@ static_assert(sizeof(rt_trace_params) == 40 && offsetof(rt_trace_params, hits) =
 int rt_trace_rays(const rt_trace_params* params, const GPUScene* scene, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Occlusion queries: "does this ray hit anything before tmax?" (shadow rays, visibility between two
+ * points, ambient occlusion, baking).  One byte per ray instead of a 48-byte record, and a traversal
+ * that ends at the first accepted primitive where that is proven safe.
+ *
+ * THE CONTRACT, WITHOUT EXCEPTION: byte i equals (kind != 0) of the record rt_trace_rays writes for
+ * ray i.  This holds for every ray and every scene, including the cases at the tmax gates, zero-length
+ * and non-finite rays, and scenes outside the filtered range.
+ *
+ * Why stopping early is safe, and where it is not.  As long as nothing has been accepted, `closest` is
+ * still tmax, and the slab test (tmin < closest), the leaf-tree cull and the triangle accept
+ * (0 <= t < closest) are all monotone in `closest`: so a first accept of any traversal order exists
+ * exactly when the reference's traversal accepts something.  That fails only where a NaN distance can be
+ * accepted: the reference's `if (dist >= closest || dist < 0) continue;` lets a NaN through, after which
+ * `closest` is NaN, nothing more is accepted, and the final `distance < max_distance` turns an earlier hit
+ * into a miss.  So a lane stops at its first accept only inside the gate within which no NaN distance can
+ * arise (the filtered range of rt_fast.h, tmax <= 1e30f, the ray's origin and the scene's root box inside
+ * +-2^16: every product of the triangle test is then finite); every other lane runs rt_trace_rays' full
+ * closest-hit traversal and reports kind != 0 && t < tmax.  The sphere loop runs in order and to the end
+ * for every lane, as in rt_trace_rays.
+ *
+ * rays: as rt_trace_rays (16-byte aligned device memory; there is no camera mode).
+ * ------------------------------------------------------------------------------------- */
+typedef struct rt_occlusion_params {
+    const rt_ray* rays;     /* DEVICE, count records, 16-byte aligned, not NULL */
+    int64_t count;          /* 0 returns at once; at most 2^31 */
+    uint8_t* occluded;      /* DEVICE, count bytes: 1 = occluded, 0 = not; bytes at and past count untouched */
+    uint32_t flags;         /* must be 0 */
+    int32_t waves_per_simd; /* occupancy build of the kernel: 5 / 6 / 7, or 0 = the measured default (7; 6 for scenes
+                               with leaf trees: profiles/occlusion_timing.txt) */
+} rt_occlusion_params;      /* 32 B */
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_occlusion_params) == 32 && offsetof(rt_occlusion_params, rays) == 0 &&
+              offsetof(rt_occlusion_params, count) == 8 && offsetof(rt_occlusion_params, occluded) == 16 &&
+              offsetof(rt_occlusion_params, flags) == 24 && offsetof(rt_occlusion_params, waves_per_simd) == 28,
+              "rt_occlusion_params");
+#endif
+
+/* Occlusion of a batch on `stream` (a hipStream_t, NULL = null stream): stream-ordered, no synchronisation,
+ * no allocation.  The scene rules are rt_trace_rays': uploaded by rt_scene_upload, a GPUScene filled by
+ * another host is rejected.  The arguments that need no device are checked first (NULL params, scene,
+ * occluded or rays; flags; waves_per_simd; count < 0 or > 2^31; alignment of rays), then the scene and
+ * the buffer sizes.  Returns 0 or an error code with rt_last_error(). */
+int rt_occluded(const rt_occlusion_params* params, const GPUScene* scene, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Ambient occlusion from the first-hit records of rt_trace_rays' camera mode: per pixel, the fraction
+ * of `samples` cosine-weighted rays of length `radius` that reach nothing.  The randomness is the
+ * caller's table of unit vectors (a normal plus a uniform point of the unit sphere, normalised, is a
+ * cosine-weighted direction), so the library holds no trigonometry and no RNG, and the arithmetic is
+ * fixed: fp32, no contraction, only + - * /, comparisons and glm's normalize (v * (1 / sqrt(dot(v, v)))),
+ * so that tests/occlusion_ref.py restates it bit for bit.  For pixel index i with rec = hits[i]:
+ *
+ *   rec.kind == 0: ao[i] = 1.0f.  Otherwise n = rec.normal, P = rec.position, e = bias * rec.t,
+ *   o = P + n * e (per component one product, then one sum), and for k = 0 .. samples - 1:
+ *     j  = (((uint32_t)i * 0x9E3779B1u + (uint32_t)k * 0x85EBCA6Bu) >> 8) % direction_count
+ *     s  = directions[j].xyz;  d0 = n + s;  dd = (d0.x*d0.x + d0.y*d0.y) + d0.z*d0.z
+ *     d  = dd > 1e-6f ? normalize(d0) : n
+ *     occ += the answer rt_occluded gives for the ray (origin o, tmax radius, direction d)
+ *   ao[i] = (float)(samples - occ) / (float)samples.
+ * ------------------------------------------------------------------------------------- */
+typedef struct rt_ao_params {
+    const rt_hit* hits;      /* DEVICE width * height records of rt_trace_rays' camera mode, 16-byte aligned */
+    int32_t width, height;   /* > 0, width * height <= 2^30 */
+    const float* directions; /* DEVICE float4[direction_count], 16-byte aligned: xyz a unit vector, w ignored */
+    int32_t direction_count; /* 1..65536 */
+    int32_t samples;         /* 1..64 */
+    float radius;            /* > 0 and not NaN (+inf allowed): tmax of every AO ray */
+    float bias;              /* >= 0, finite: origin offset along the normal, as a fraction of the hit distance */
+    float* ao;               /* DEVICE width * height floats, record order */
+    void* scratch;           /* DEVICE, rt_ao_scratch_bytes(width, height, samples); may be NULL when that is 0 */
+    uint64_t scratch_bytes;
+    uint32_t flags;          /* must be 0 */
+    int32_t waves_per_simd;  /* 0 = the measured default, 5 / 6 / 7, as rt_occlusion_params */
+} rt_ao_params;              /* 72 B */
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_ao_params) == 72 && offsetof(rt_ao_params, hits) == 0 && offsetof(rt_ao_params, width) == 8 &&
+              offsetof(rt_ao_params, height) == 12 && offsetof(rt_ao_params, directions) == 16 &&
+              offsetof(rt_ao_params, direction_count) == 24 && offsetof(rt_ao_params, samples) == 28 &&
+              offsetof(rt_ao_params, radius) == 32 && offsetof(rt_ao_params, bias) == 36 && offsetof(rt_ao_params, ao) == 40 &&
+              offsetof(rt_ao_params, scratch) == 48 && offsetof(rt_ao_params, scratch_bytes) == 56 &&
+              offsetof(rt_ao_params, flags) == 64 && offsetof(rt_ao_params, waves_per_simd) == 68,
+              "rt_ao_params");
+#endif
+
+/* Bytes of scratch rt_ao needs: 0 for every size (one fused kernel loops over a pixel's samples and keeps the
+ * count in a register), so also 0 for a size <= 0, and monotone. */
+size_t rt_ao_scratch_bytes(int width, int height, int samples);
+/* AO on `stream`: stream-ordered, no synchronisation, no allocation, one kernel launch.  Every argument is
+ * checked on the host before the launch; the scene rules are rt_occluded's.  Returns 0 or an error code with
+ * rt_last_error(). */
+int rt_ao(const rt_ao_params* params, const GPUScene* scene, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Denoising: a viewable image from one low-sample frame and the first-hit records of its camera
  * (render -> rt_trace_rays in camera mode -> rt_denoise).  An edge-avoiding a-trous wavelet filter on
  * the frame divided by the first hit's albedo, guided by normal, position and distance; the albedo

@@ -4,11 +4,14 @@
     python tools/render_image.py [--config cfg2] [--frames 4] [--out gpurun_out/cfg2]
     python tools/render_image.py --aov PREFIX
     python tools/render_image.py --denoise
+    python tools/render_image.py --ao RADIUS
 
 --aov PREFIX also writes the first-hit images of the same camera (rt.gbuffer: pixel centres, no jitter) as
 PREFIX_normal.pfm (normal * 0.5 + 0.5), PREFIX_depth.pfm (hit distance, inf on a miss) and PREFIX_albedo.pfm.
 --denoise also writes OUT_denoised.pfm / .ppm next to the beauty frame: rt.denoise of the last frame, guided by the
 same camera's first-hit records, into a surface of its own (the progressive history is not touched).
+--ao RADIUS also writes OUT_ao.pfm (linear) / .ppm (8-bit, linear grey): rt.ambient_occlusion of the same camera's
+first-hit records, 8 samples per pixel of length RADIUS (1 = open, 0 = closed, 1 where the camera ray missed).
 """
 import argparse
 import os
@@ -22,6 +25,16 @@ import __graft_entry__ as G  # noqa: E402
 import bench  # noqa: E402
 
 
+def ao_outputs(ao):
+    """An AO image [H, W] in record order (row 0 = the bottom of the frame, as the surface) as what the two writers
+    take: (float32 [H, W * 4] grey RGBA, bottom to top, for write_pfm; uint8 [H, W, 3] linear grey, TOP to bottom,
+    for write_ppm -- the beauty frame's rows are flipped by tonemap, these here)."""
+    h, w = ao.shape
+    grey = ao[:, :, None].expand(h, w, 3)
+    rgba = torch.cat([grey, torch.ones((h, w, 1), dtype=torch.float32, device=ao.device)], dim=2)
+    return rgba.reshape(h, w * 4), (grey.flip(0) * 255.0 + 0.5).to(torch.uint8)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="cfg2")
@@ -29,6 +42,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "frame"))
     ap.add_argument("--aov", default=None, metavar="PREFIX")
     ap.add_argument("--denoise", action="store_true")
+    ap.add_argument("--ao", type=float, default=None, metavar="RADIUS")
     args = ap.parse_args()
     rt = G.load_package()
     scene_name, W, H, SPP, BOUNCES, _ = bench.CONFIGS[args.config]
@@ -52,6 +66,12 @@ def main():
         rt.write_pfm(args.out + "_denoised.pfm", clean, W, H)
         rt.write_ppm(args.out + "_denoised.ppm", rt.tonemap(clean, W, H))
         print(f"wrote {args.out}_denoised.pfm / .ppm")
+    if args.ao is not None:
+        ao = rt.ambient_occlusion(scene, rt.trace_camera(scene, W, H), W, H, args.ao)
+        pfm, ppm = ao_outputs(ao)
+        rt.write_pfm(args.out + "_ao.pfm", pfm, W, H)
+        rt.write_ppm(args.out + "_ao.ppm", ppm)
+        print(f"wrote {args.out}_ao.pfm / .ppm (radius {args.ao:g}, 8 samples)")
     if args.aov:
         g = rt.gbuffer(scene, W, H)
         images = {"normal": g["normal"] * 0.5 + 0.5,
