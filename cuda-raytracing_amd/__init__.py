@@ -124,6 +124,16 @@ class DenoiseParams(ctypes.Structure):
                 ("normal_power_log2", ctypes.c_int32), ("sigma_plane", ctypes.c_float), ("sigma_color", ctypes.c_float)]
 
 
+class ReprojectParams(ctypes.Structure):
+    """rt_reproject_params (rt_abi.h)."""
+    _fields_ = [("surface", ctypes.c_void_p), ("pitch", ctypes.c_uint64), ("hits", ctypes.c_void_p),
+                ("prev_surface", ctypes.c_void_p), ("prev_pitch", ctypes.c_uint64), ("prev_hits", ctypes.c_void_p),
+                ("prev_history", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_pitch", ctypes.c_uint64),
+                ("out_history", ctypes.c_void_p), ("camera", GPUCamera), ("prev_camera", GPUCamera),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("max_history", ctypes.c_int32),
+                ("sigma_plane", ctypes.c_float), ("normal_min", ctypes.c_float), ("flags", ctypes.c_int32)]
+
+
 HIT_MISS, HIT_SPHERE, HIT_TRIANGLE = 0, 1, 2  # rt_hit.kind
 RAY_TMAX = 1e30  # the renderer's own initial closest distance (main_raytracing.cu:85)
 DENOISE_DEFAULT = -1  # RT_DENOISE_DEFAULT: in a filter parameter of rt_denoise, the measured default
@@ -133,6 +143,10 @@ DENOISE_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_plane": 0.03
 assert ctypes.sizeof(GPUScene) == 136 and ctypes.sizeof(GPUMaterial) == 64
 assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(Hit) == 48 and ctypes.sizeof(TraceParams) == 40
 assert ctypes.sizeof(DenoiseParams) == 96 and ctypes.sizeof(OcclusionParams) == 32 and ctypes.sizeof(AoParams) == 72
+REPROJECT_DEFAULT = -1  # RT_REPROJECT_DEFAULT: in a filter parameter of rt_reproject, the measured default
+# the defaults rt_reproject substitutes (csrc/reproject.hip; profiles/reproject_quality.txt)
+REPROJECT_DEFAULTS = {"max_history": 32, "sigma_plane": 0.03, "normal_min": 0.9}
+assert ctypes.sizeof(ReprojectParams) == 224 and ctypes.sizeof(GPUCamera) == 60
 
 # name -> (restype, argtypes); every symbol include/rt_abi.h declares.
 _P, _I, _U32, _U64, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_size_t
@@ -147,6 +161,7 @@ SIGNATURES = {
     "rt_ao": (_I, [ctypes.POINTER(AoParams), _P, _P]),
     "rt_denoise_scratch_bytes": (_SZ, [_I, _I]),
     "rt_denoise": (_I, [ctypes.POINTER(DenoiseParams), _P]),
+    "rt_reproject": (_I, [ctypes.POINTER(ReprojectParams), _P]),
     "rt_foreign_mirror_wait": (_I, [_P]),
     "rt_foreign_last_tracer": (_I, [_P]),
     "rt_experimental_loaded": (_I, []),
@@ -762,6 +777,119 @@ def denoise(scene, surface, width, height, hits=None, out=None, scratch=None, it
                     normal_power_log2, sigma_plane, sigma_color, stream)
 
 
+def _as_camera(camera):
+    """A GPUCamera from a GPUCamera or 15 floats in its layout (origin, viewport size, aspect, horizontal,
+    vertical, lower-left corner)."""
+    if isinstance(camera, GPUCamera):
+        return camera
+    v = np.ascontiguousarray(camera, dtype=np.float32).reshape(-1)
+    assert v.size == 15, "a camera is a GPUCamera or 15 floats"
+    return GPUCamera.from_buffer_copy(v.tobytes())
+
+
+def camera_floats(camera):
+    """The 15 floats of a GPUCamera as a numpy float32 array."""
+    return np.frombuffer(bytes(_as_camera(camera)), dtype=np.float32).copy()
+
+
+def _is_surface(t, w, h):
+    return (t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= h
+            and t.shape[1] >= 4 * w)
+
+
+def _is_hits(t, w, h):
+    return (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 12
+            and t.shape[0] >= w * h)
+
+
+def _is_history(t, w, h):
+    return t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() >= w * h
+
+
+def reproject_raw(surface, hits, camera, width, height, prev=None, out=None, out_history=None,
+                  max_history=REPROJECT_DEFAULT, sigma_plane=REPROJECT_DEFAULT, normal_min=REPROJECT_DEFAULT, stream=None):
+    """rt_reproject on tensors only: `surface` a pitched float4 surface holding a frame rendered with frame_index 0,
+    `hits` the float32 [H*W, 12] records of trace_camera for `camera` (a GPUCamera, as Scene.camera() returns it after
+    the upload, or its 15 floats).  `prev` = (prev_surface, prev_hits, prev_history, prev_camera): what the previous
+    call returned and was given; None on the first frame.  Returns (out, out_history): the accumulated surface and
+    the float32 [H, W] number of frames it holds per pixel (new tensors when None; `out is surface` is allowed,
+    `out is prev_surface` is not).  A filter parameter left at REPROJECT_DEFAULT takes the library's default
+    (REPROJECT_DEFAULTS).  Stream-ordered on `stream` (default: torch's current stream); tensors allocated here are
+    allocated on that stream, tensors passed in must be safe to use on it."""
+    w, h = int(width), int(height)
+    assert _is_surface(surface, w, h) and _is_hits(hits, w, h)
+    with _allocating_on(stream):
+        if out is None:
+            out = alloc_surface(w, h, device=surface.device)
+        if out_history is None:
+            out_history = torch.zeros((h, w), dtype=torch.float32, device=surface.device)
+    assert _is_surface(out, w, h) and _is_history(out_history, w, h)
+    p = ReprojectParams()
+    p.surface, p.pitch, p.hits = surface.data_ptr(), surface.stride(0) * 4, hits.data_ptr()
+    p.out, p.out_pitch, p.out_history = out.data_ptr(), out.stride(0) * 4, out_history.data_ptr()
+    p.camera = _as_camera(camera)
+    if prev is not None:
+        prev_surface, prev_hits, prev_history, prev_camera = prev
+        assert _is_surface(prev_surface, w, h) and _is_hits(prev_hits, w, h) and _is_history(prev_history, w, h)
+        p.prev_surface, p.prev_pitch = prev_surface.data_ptr(), prev_surface.stride(0) * 4
+        p.prev_hits, p.prev_history = prev_hits.data_ptr(), prev_history.data_ptr()
+        p.prev_camera = _as_camera(prev_camera)
+    p.width, p.height = w, h
+    p.max_history, p.sigma_plane, p.normal_min = int(max_history), float(sigma_plane), float(normal_min)
+    _check(lib().rt_reproject(ctypes.byref(p), _stream_ptr(stream)), "rt_reproject")
+    return out, out_history
+
+
+class TemporalAccumulator:
+    """Temporal accumulation of a moving camera's frames (rt_reproject): two accumulated surfaces, two histories
+    and two hit buffers used in turn, plus the previous camera.  **filter_params are reproject_raw's max_history,
+    sigma_plane and normal_min.  Static geometry only."""
+
+    def __init__(self, width, height, **filter_params):
+        assert not set(filter_params) - set(REPROJECT_DEFAULTS), sorted(set(filter_params) - set(REPROJECT_DEFAULTS))
+        self.width, self.height = int(width), int(height)
+        self.filter_params = dict(filter_params)
+        self._slots = [None, None]  # (surface, hits, history), allocated at first use
+        self.reset()
+
+    def reset(self):
+        """Forget the history: the next push starts a new accumulation."""
+        self._latest = None  # index of the slot the last push wrote
+        self._camera = None
+
+    def push(self, scene, surface, hits=None, stream=None):
+        """Accumulate `surface`, a frame of the uploaded `scene`'s current camera rendered with frame_index 0; `hits`:
+        that camera's trace_camera records (traced here when None).  Returns the accumulated surface, which stays
+        valid until the next-but-one push."""
+        w, h = self.width, self.height
+        camera = scene.camera()
+        k = 0 if self._latest is None else 1 - self._latest
+        with _allocating_on(stream):
+            if self._slots[k] is None:
+                self._slots[k] = (alloc_surface(w, h, device=surface.device),
+                                  torch.empty((w * h, 12), dtype=torch.float32, device=surface.device),
+                                  torch.zeros((h, w), dtype=torch.float32, device=surface.device))
+            out, own_hits, history = self._slots[k]
+            if hits is None:
+                trace_camera(scene, w, h, hits=own_hits, stream=stream)
+            else:
+                assert _is_hits(hits, w, h)
+                own_hits.copy_(hits[: w * h])
+        prev = None
+        if self._latest is not None:
+            prev = (*self._slots[self._latest], self._camera)
+        reproject_raw(surface, own_hits, camera, w, h, prev=prev, out=out, out_history=history, stream=stream,
+                      **self.filter_params)
+        self._latest, self._camera = k, camera
+        return out
+
+    @property
+    def history(self):
+        """[H, W] view of the latest history: the number of frames the latest accumulated surface holds per pixel
+        (None before the first push)."""
+        return None if self._latest is None else self._slots[self._latest][2]
+
+
 def foreign_mirror_wait(gpu_scene):
     """rt_foreign_mirror_wait: block until the background mirror build of a foreign GPUScene (a
     ctypes GPUScene filled by the caller) has finished; the next render installs it."""
@@ -967,6 +1095,7 @@ class RayTracer:
         self.last_frame = alloc_surface(width, height)
         self.rng = None
         self.frame_index = 0
+        self._accumulator = None  # reprojected()'s TemporalAccumulator
 
     def on_resize(self, width, height):
         self.width, self.height = width, height
@@ -974,6 +1103,7 @@ class RayTracer:
         self.last_frame = alloc_surface(width, height)
         self.rng = None
         self.frame_index = 0
+        self._accumulator = None
 
     def process(self, stats=None):
         if self.rng is None:
@@ -1015,6 +1145,22 @@ class RayTracer:
             with _allocating_on(stream):
                 hits = trace_camera(self.scene, self.width, self.height, stream=stream)
         return ambient_occlusion(self.scene, hits, self.width, self.height, radius, **kw)
+
+    def reprojected(self, **kw):
+        """The current frame accumulated with the frames of earlier calls, whatever cameras they had (a lazily
+        created TemporalAccumulator; **kw are its filter parameters, and push's hits and stream).  Meant for frames
+        rendered with frame_index == 0: set ``tracer.frame_index = 0`` after moving the camera, as the reference's
+        Process() does on its dirty flag, then process(), then this.  Returns the accumulated surface, valid until
+        the next-but-one call.  Uploads the scene like process(); `surface`, `last_frame`, the RNG states and the
+        frame index are left alone.  on_resize drops the accumulator."""
+        self.scene.set_viewport(self.width, self.height)
+        self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
+        push_kw = {k: kw.pop(k) for k in ("hits", "stream") if k in kw}
+        if self._accumulator is None:
+            self._accumulator = TemporalAccumulator(self.width, self.height)
+        assert not set(kw) - set(REPROJECT_DEFAULTS), sorted(set(kw) - set(REPROJECT_DEFAULTS))
+        self._accumulator.filter_params.update(kw)
+        return self._accumulator.push(self.scene, self.surface, **push_kw)
 
     def save(self, path):
         """The current frame: ``.pfm`` linear RGB, ``.ppm`` as the reference's viewer shows it

@@ -529,6 +529,98 @@ size_t rt_denoise_scratch_bytes(int width, int height);
  * `out` must not overlap scratch or hits.  Returns 0 or an error code with rt_last_error(). */
 int rt_denoise(const rt_denoise_params* params, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Temporal accumulation across camera moves: the samples of earlier frames carried into the new camera's
+ * frame (render with frame_index 0 -> rt_trace_rays in camera mode -> rt_reproject -> rt_denoise).  Each
+ * call's `out`, `out_history` and `hits` (with its camera) are the next call's prev_*.  The new frame's
+ * first-hit points are projected into the previous camera's viewport; the previous image is gathered there
+ * bilinearly from the taps whose own first-hit record agrees, and the new frame joins a running mean whose
+ * length is kept per pixel.  Static geometry only: there are no motion vectors for objects.
+ *
+ * The arithmetic is fixed (fp32, no contraction, IEEE division, only + - * /, floorf, fminf, fabsf and
+ * comparisons), so that tests/reproject_ref.py restates it bit for bit.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z,
+ * cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x).
+ *
+ * Per-frame constants (host, fp32) from prev_camera, O, H, V, L = origin, horizontal, vertical, lower_left_corner:
+ *   w = L - O, N = cross(H, V), A = cross(V, w), B = cross(w, H), wn = dot(w, N).
+ * For a direction d from O the previous viewport coordinates are u = dot(d, A) / dn, v = dot(d, B) / dn with
+ * dn = dot(d, N): Cramer's rule on O + s d = L + u H + v V, which needs no orthogonality of H and V.
+ *
+ * Per pixel p = (x, y), i = y * width + x, rec = hits[i], cur = surface[p]:
+ *  1. rec.kind != 0: d = rec.position - O.  rec.kind == 0: d = the current camera's pixel-centre ray direction
+ *     exactly as rt_trace_rays' camera mode forms it (above), so sky is reprojected as being at infinity.
+ *  2. dn = dot(d, N), s = wn / dn, fx = (dot(d, A) / dn) * (float)width - 0.5f, fy = (dot(d, B) / dn) *
+ *     (float)height - 0.5f.  The projection is valid iff dn != 0 && s > 0 && fx > -1 && fx < width && fy > -1 &&
+ *     fy < height (NaN fails every comparison).  Only a valid projection is converted to integers:
+ *     x0 = (int)floorf(fx), ax = fx - floorf(fx), y0 and ay likewise.
+ *  3. Four taps in the order (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), weight w = wx * wy with
+ *     wx = 1.0f - ax or ax, wy = 1.0f - ay or ay.  A tap q is taken iff it is inside the image, w > 0,
+ *     prev_history[q] >= 1.0f, prev_surface[q].rgb is finite, and
+ *       for a miss pixel: prev_hits[q].kind == 0;
+ *       for a hit pixel:  prev_hits[q].kind != 0, prev_hits[q].material == rec.material,
+ *                         dot(n_p, n_q) >= normal_min and fabsf(dot(n_p, pos_q - rec.position)) <= sigma_plane * rec.t.
+ *     Face ids are deliberately not compared: every loaded face exists twice, wound both ways.
+ *     A taken tap adds sum += c_q * w, hs += prev_history[q] * w, ws += w.
+ *  4. With history (ws > 0): pc = sum / ws, hl = hs / ws.
+ *       cur.rgb finite:     n = fminf(hl + 1.0f, (float)max_history), out.rgb = pc + (cur.rgb - pc) * (1.0f / n),
+ *                           out_history = n;
+ *       cur.rgb not finite: out.rgb = pc, out_history = fminf(hl, (float)max_history)  (the history heals the pixel).
+ *  5. Without history (invalid projection, ws == 0, or NULL prev): out.rgb = cur.rgb, out_history = 1, or 0 when
+ *     cur.rgb is not finite -- such a pixel is never taken as history, so poison cannot spread.
+ *  6. out.a = cur.a always.  Row padding of `out` is never written.
+ *
+ * PITFALL: render the frames fed to this with frame_index 0 (as the reference's Process() does while its sample
+ * flag is dirty); a frame that rt_render has already blended with surface_last_frame would be counted twice.
+ * ------------------------------------------------------------------------------------- */
+#define RT_REPROJECT_DEFAULT (-1)  /* in any of the three filter parameters: the measured default */
+#define RT_REPROJECT_MAX_HEIGHT RT_DENOISE_MAX_HEIGHT  /* the launch grid holds a row of blocks per 4 pixel rows */
+#define RT_REPROJECT_MAX_PIXELS RT_DENOISE_MAX_PIXELS
+
+typedef struct rt_reproject_params {
+    const void* surface;           /* DEVICE pitched float4: the new frame, rendered with frame_index 0 */
+    uint64_t pitch;                /* bytes per row: >= width * 16, a multiple of 16 (all three pitches) */
+    const rt_hit* hits;            /* DEVICE width * height records of rt_trace_rays' camera mode for `camera` */
+    /* The previous call's results: all three NULL (first frame, no history) or all three non-NULL. */
+    const void* prev_surface;      /* DEVICE pitched float4: the previous accumulated image */
+    uint64_t prev_pitch;
+    const rt_hit* prev_hits;       /* DEVICE: the previous camera's records; prev_hits == hits is allowed */
+    const float* prev_history;     /* DEVICE width * height floats: frames the previous image holds per pixel */
+    void* out;                     /* DEVICE pitched float4: the new accumulated image; out == surface is allowed */
+    uint64_t out_pitch;
+    float* out_history;            /* DEVICE width * height floats */
+    GPUCamera camera;              /* as rt_scene_camera returns them after the upload of each frame */
+    GPUCamera prev_camera;         /* (ignored when prev_* are NULL) */
+    int32_t width, height;         /* > 0; height <= RT_REPROJECT_MAX_HEIGHT, width * height <= RT_REPROJECT_MAX_PIXELS */
+    /* Filter parameters.  RT_REPROJECT_DEFAULT (-1, -1.0f) selects the default (profiles/reproject_quality.txt);
+     * so a normal_min of exactly -1 cannot be asked for -- -0.999999f switches the normal test off just as well. */
+    int32_t max_history;           /* 1..65535 (32): the running mean never weighs a new frame below 1 / this */
+    float sigma_plane;             /* > 0, finite (0.03): tolerated distance of a tap from p's tangent plane, as a fraction of t_p */
+    float normal_min;              /* [-1, 1] (0.9): least cosine between p's normal and a tap's */
+    int32_t flags;                 /* must be 0 */
+} rt_reproject_params;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_reproject_params) == 224 && offsetof(rt_reproject_params, surface) == 0 &&
+              offsetof(rt_reproject_params, pitch) == 8 && offsetof(rt_reproject_params, hits) == 16 &&
+              offsetof(rt_reproject_params, prev_surface) == 24 && offsetof(rt_reproject_params, prev_pitch) == 32 &&
+              offsetof(rt_reproject_params, prev_hits) == 40 && offsetof(rt_reproject_params, prev_history) == 48 &&
+              offsetof(rt_reproject_params, out) == 56 && offsetof(rt_reproject_params, out_pitch) == 64 &&
+              offsetof(rt_reproject_params, out_history) == 72 && offsetof(rt_reproject_params, camera) == 80 &&
+              offsetof(rt_reproject_params, prev_camera) == 140 && offsetof(rt_reproject_params, width) == 200 &&
+              offsetof(rt_reproject_params, height) == 204 && offsetof(rt_reproject_params, max_history) == 208 &&
+              offsetof(rt_reproject_params, sigma_plane) == 212 && offsetof(rt_reproject_params, normal_min) == 216 &&
+              offsetof(rt_reproject_params, flags) == 220,
+              "rt_reproject_params");
+#endif
+
+/* Reproject and accumulate on `stream` (a hipStream_t, NULL = null stream): stream-ordered, no synchronisation, no
+ * allocation, no scene, no scratch; one kernel launch.  Every argument is checked on the host before the launch
+ * (NULL pointers, prev_* partly NULL, sizes <= 0 or above the limits, pitches, alignment -- 16 bytes for surfaces and
+ * records, 4 for the histories --, flags != 0, parameters out of range).  out == surface is safe: a lane reads only its
+ * own pixel of `surface` before it writes.  `out` overlapping prev_surface and out_history overlapping prev_history
+ * are refused: other lanes gather from them.  Returns 0 or an error code with rt_last_error(). */
+int rt_reproject(const rt_reproject_params* params, void* stream);
+
 /* init_rng for the pixels of one shard: state index s of shard (shard_index, shard_count)
  * of a width x height frame gets curand_init(seed, pixel_id(s), 0).  With shard_count == 1
  * the states are in y*width + x order (reference layout); otherwise they are compact in the

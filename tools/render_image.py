@@ -5,6 +5,7 @@
     python tools/render_image.py --aov PREFIX
     python tools/render_image.py --denoise
     python tools/render_image.py --ao RADIUS
+    python tools/render_image.py --temporal K
 
 --aov PREFIX also writes the first-hit images of the same camera (rt.gbuffer: pixel centres, no jitter) as
 PREFIX_normal.pfm (normal * 0.5 + 0.5), PREFIX_depth.pfm (hit distance, inf on a miss) and PREFIX_albedo.pfm.
@@ -12,6 +13,8 @@ PREFIX_normal.pfm (normal * 0.5 + 0.5), PREFIX_depth.pfm (hit distance, inf on a
 same camera's first-hit records, into a surface of its own (the progressive history is not touched).
 --ao RADIUS also writes OUT_ao.pfm (linear) / .ppm (8-bit, linear grey): rt.ambient_occlusion of the same camera's
 first-hit records, 8 samples per pixel of length RADIUS (1 = open, 0 = closed, 1 where the camera ray missed).
+--temporal K also writes OUT_temporal.pfm / .ppm: K frames of the config's spp, each rendered with frame_index 0 along a
+small camera dolly that ends at the config's camera, accumulated by rt.TemporalAccumulator (rt_reproject).
 """
 import argparse
 import os
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--aov", default=None, metavar="PREFIX")
     ap.add_argument("--denoise", action="store_true")
     ap.add_argument("--ao", type=float, default=None, metavar="RADIUS")
+    ap.add_argument("--temporal", type=int, default=None, metavar="K")
     args = ap.parse_args()
     rt = G.load_package()
     scene_name, W, H, SPP, BOUNCES, _ = bench.CONFIGS[args.config]
@@ -72,6 +76,20 @@ def main():
         rt.write_pfm(args.out + "_ao.pfm", pfm, W, H)
         rt.write_ppm(args.out + "_ao.ppm", ppm)
         print(f"wrote {args.out}_ao.pfm / .ppm (radius {args.ao:g}, 8 samples)")
+    if args.temporal is not None:
+        assert args.temporal >= 1
+        acc = rt.TemporalAccumulator(W, H)
+        frame, unused = rt.alloc_surface(W, H), rt.alloc_surface(W, H)
+        for k in range(args.temporal):
+            b = args.temporal - 1 - k  # steps before the config's camera (position 0, angles 0 / 180)
+            scene.set_camera((-0.05 * b, -0.02 * b, -0.04 * b), 0.1 * b, 180.0 - 0.25 * b)
+            scene.upload(rng.data_ptr())
+            rt.render(scene, frame, unused, W, H, SPP, BOUNCES, 0)
+            moving = acc.push(scene, frame)
+        rt.write_pfm(args.out + "_temporal.pfm", moving, W, H)
+        rt.write_ppm(args.out + "_temporal.ppm", rt.tonemap(moving, W, H))
+        print(f"wrote {args.out}_temporal.pfm / .ppm ({args.temporal} frames x {SPP} spp along a dolly; "
+              f"mean history {float(acc.history.mean()):.1f} frames)")
     if args.aov:
         g = rt.gbuffer(scene, W, H)
         images = {"normal": g["normal"] * 0.5 + 0.5,
