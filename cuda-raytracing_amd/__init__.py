@@ -226,6 +226,7 @@ SIGNATURES = {
                                    ctypes.POINTER(_SZ), ctypes.POINTER(_P), ctypes.POINTER(_SZ), ctypes.POINTER(_P)]),
     "rt_scene_bvh_max_depth": (_I, [_P]),
     "rt_scene_materials": (_I, [_P, _P, ctypes.POINTER(_SZ)]),
+    "rt_scene_spheres": (_I, [_P, _P, ctypes.POINTER(_SZ)]),
     "rt_bvh_build_device": (_I, [_P, _U32, _P, _U32, _P, _P, ctypes.POINTER(_U32), ctypes.POINTER(_I), _P]),
     "rt_scene_mirror_info": (_I, [_P, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
     "rt_scene_mirror_copy": (_I, [_P, _P, _P, _P]),
@@ -433,6 +434,15 @@ class Scene:
         out = np.zeros((n.value, 16), dtype=np.float32)
         if n.value:
             _check(lib().rt_scene_materials(self.handle, out.ctypes.data, ctypes.byref(n)), "rt_scene_materials")
+        return out
+
+    def spheres(self):
+        """Host copy of the sphere array as (S, 8) float32: centre 0-2, radius, material (an int32), padding."""
+        n = ctypes.c_size_t()
+        _check(lib().rt_scene_spheres(self.handle, None, ctypes.byref(n)), "rt_scene_spheres")
+        out = np.zeros((n.value, 8), dtype=np.float32)
+        if n.value:
+            _check(lib().rt_scene_spheres(self.handle, out.ctypes.data, ctypes.byref(n)), "rt_scene_spheres")
         return out
 
     def host_arrays(self):

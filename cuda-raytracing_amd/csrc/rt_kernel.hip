@@ -56,6 +56,14 @@ static int check(hipError_t e, const char* what) {
 
 extern "C" const char* rt_last_error(void) { return g_last_error.c_str(); }
 
+// A BVH deeper than the largest traversal stack holds (rt_variant.h kMaxBvhDepth) reaches no kernel: `who` refuses it.
+static bool depth_refused(const char* who, int depth) {
+    if (depth <= rtk::kMaxBvhDepth) return false;
+    set_error(std::string(who) + ": the scene's BVH is " + std::to_string(depth) + " levels deep; the traversal stack holds depth <= " +
+              std::to_string(rtk::kMaxBvhDepth) + " (rebuild the scene with fewer nested triangles)");
+    return true;
+}
+
 // Bytes of the device allocation holding p from p to its end (0 if p is not device memory).
 static size_t bytes_from(const void* p) {
     hipDeviceptr_t base = nullptr;
@@ -819,6 +827,7 @@ extern "C" int rt_render(const rt_render_params* p, const GPUScene* scene, void*
     }
     const void* tris = mir.tris;
     const int depth = mir.depth;
+    if (depth_refused("rt_render", depth)) return 1;  // before any launch, the reference-layout tracers' included
     const bool scene_fast = mir.fast;
     a.tune = p->tune;  // diagnostic A/B knobs; 0 = the production path
     a.pairs = (a.tune & 2u) ? nullptr : (const float4*)mir.pairs;
@@ -944,6 +953,7 @@ static int query_scene(const char* who, const GPUScene* scene, QueryArgs* out, V
         return set_error(w + ": this GPUScene was not uploaded by rt_scene_upload (a foreign scene has no private "
                              "mirror to query; foreign scenes are not supported here)");
     if (!mir.nodes || !mir.tris) return set_error(w + ": the scene's mirror has no triangles to traverse");
+    if (depth_refused(who, mir.depth)) return 1;
     if (scene->sphere_count > 0 && !scene->gpu_spheres) return set_error(w + ": sphere_count without spheres");
     QueryArgs q;
     std::memset(&q, 0, sizeof(q));

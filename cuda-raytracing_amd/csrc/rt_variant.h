@@ -68,6 +68,11 @@ constexpr int kEntryStackExtra = 14;
 
 // The traversal stack for a BVH of `depth`: the DFS holds at most depth + 1 entries (+ extra); 30 entries -- 7.5 KB
 // of LDS per wave -- still fit 5 waves per SIMD and cover the 4-bunny scene's depth 28.
+// The deepest BVH any traversal kernel is launched on: the largest STACK is 64 entries and the walk needs depth + 2
+// (rtfast::Stack::put has no bound of its own -- a deeper tree would write past its arrays).  rt_render, rt_trace_rays,
+// rt_occluded and rt_ao refuse a deeper scene (rt_kernel.hip depth_refused) before anything is launched.
+constexpr int kMaxBvhDepth = 62;
+
 inline int variant_stack(int depth, int extra = 0) {
     const int need = depth + 2 + extra;
     return (depth >= 0 && need <= 30) ? 30 : (depth >= 0 && need <= 40) ? 40 : 64;

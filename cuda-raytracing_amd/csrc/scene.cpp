@@ -306,6 +306,11 @@ static constexpr size_t kGpuBvhMinFaces = 65536;
 
 // Scene.cpp:182-234
 void Scene::Upload(void* rng) {
+    // BVH::Calculate gives a scene without triangles one root with prim_count 0: to BVHRayHit an inner node whose
+    // children are nodes 0 and 1 (itself, and one past the array), with inverted bounds the fmin / fmax slab test
+    // does not reject -- no tracer terminates on it.  Refused here, before any device state exists, so no
+    // entry point is ever handed such a scene.
+    if (faces.empty()) throw std::runtime_error("the scene has no triangles to traverse (spheres alone cannot be rendered)");
     rt_build_options opt;
     rt_get_build_options(&opt);
     const bool host_bvh = opt.host_bvh != 0;
@@ -673,6 +678,7 @@ int rt_scene_upload(rt_scene* s, void* rng_state) {
         s->scene.Upload(rng_state);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "rt_scene_upload: %s\n", e.what());
+        rt_internal_set_error((std::string("rt_scene_upload: ") + e.what()).c_str());
         return 1;
     }
     return 0;
@@ -743,6 +749,16 @@ int rt_scene_materials(rt_scene* s, void* out, size_t* count) {
         for (size_t i = 0; i < gm.size(); i++)
             std::memcpy((char*)out + i * sizeof(GPUMaterial), &gm[i], offsetof(GPUMaterial, IOR) + sizeof(float));
     }
+    return 0;
+}
+int rt_scene_spheres(rt_scene* s, void* out, size_t* count) {
+    if (!s || !count) {
+        rt_internal_set_error("rt_scene_spheres: null argument");
+        return -1;
+    }
+    const auto& sp = s->scene.HostSpheres();
+    *count = sp.size();
+    if (out && !sp.empty()) std::memcpy(out, sp.data(), sp.size() * sizeof(sp[0]));
     return 0;
 }
 void rt_scene_build(rt_scene* s) { s->scene.BuildHost(); }

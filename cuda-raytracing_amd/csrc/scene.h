@@ -130,6 +130,7 @@ struct Scene : public GPUScene {
 
     const std::vector<GPUVertex>& HostVertices() const { return vertices; }
     const std::vector<GPUFace>& HostFaces() const { return faces; }
+    const std::vector<GeometrySphere>& HostSpheres() const { return spheres; }
     std::vector<GPUMaterial> HostMaterials() const { return std::vector<GPUMaterial>(materials.begin(), materials.end()); }
     const BVH& GetBVH() const { return *bvh; }
 

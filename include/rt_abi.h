@@ -769,7 +769,9 @@ int rt_scene_set_environment_file(rt_scene* scene, const char* path);
 int rt_scene_environment(const rt_scene* scene, const float** texels, int* size);
 void rt_scene_set_camera(rt_scene* scene, const float position[3], float angle_x_deg, float angle_y_deg);
 void rt_scene_set_viewport(rt_scene* scene, int width, int height);
-/* Scene::Upload: builds the BVH when dirty, uploads dirty buffers, fills the GPUScene. */
+/* Scene::Upload: builds the BVH when dirty, uploads dirty buffers, fills the GPUScene.  0, or 1 with
+ * rt_last_error(): a scene without triangles is refused here, before any device state exists (no tracer
+ * terminates on the lone root BVH::Calculate gives it). */
 int rt_scene_upload(rt_scene* scene, void* rng_state);
 const GPUScene* rt_scene_gpu(const rt_scene* scene);
 /* The host half of Scene::Upload without any device work: camera basis + BVH build. */
@@ -786,10 +788,17 @@ int rt_scene_setup_plane(rt_scene* scene, int n, const char* assets_dir);
 size_t rt_scene_host_arrays(const rt_scene* scene, const GPUBVHNode** nodes, size_t* node_count,
                             const uint32_t** face_indices, size_t* face_count, const GPUVertex** vertices,
                             size_t* vertex_count, const GPUFace** faces);
+/* The BVH's depth.  rt_render, rt_trace_rays, rt_occluded and rt_ao refuse a scene deeper than 62 levels (the
+ * traversal stacks hold depth + 2 <= 64 entries; csrc/rt_variant.h kMaxBvhDepth) with an error that names the limit,
+ * before anything is launched.  rt_scene_upload refuses a scene without triangles. */
 int rt_scene_bvh_max_depth(const rt_scene* scene);
 /* Host copy of the scene's GPUMaterial array (what rt_hit.material indexes): *count receives the
  * material count; out (may be NULL) receives the records.  0 or -1 with rt_last_error(). */
 int rt_scene_materials(rt_scene* scene, void* out, size_t* count);
+/* Host copy of the scene's sphere array (what rt_hit.id indexes on a sphere hit), 32 bytes each: centre[3], radius,
+ * material (int32), 12 bytes of padding.  *count receives the sphere count; out (may be NULL) receives the records.
+ * 0 or -1 with rt_last_error(). */
+int rt_scene_spheres(rt_scene* scene, void* out, size_t* count);
 
 /* Build options (process-wide; affect later rt_scene_upload / mirror builds and
  * rt_bvh_build_device calls).  None of them changes a rendered bit -- the leaf trees and the GPU

@@ -54,6 +54,21 @@ def oracle():
         L.oracle_sin.restype = L.oracle_cos.restype = _F
         L.oracle_render.restype = _I
         L.oracle_render.argtypes = [_P, _I, _I, _I, _I, _I, _U32, _P, _P, _P, _I, _I, _I, _P]
+        # the scene builder (rt_oracle.c "Scene builder for tests") and the per-pixel pending-entry maximum
+        _FP = ctypes.POINTER(_F)
+        L.oracle_scene_new.restype = _P
+        L.oracle_scene_new.argtypes = []
+        L.oracle_scene_add_material.argtypes = [_P, _FP]
+        L.oracle_scene_add_triangle.argtypes = [_P, _FP, _FP, _FP, _I]
+        L.oracle_scene_add_quad.argtypes = [_P, _FP, _FP, _FP, _FP, _I]
+        L.oracle_scene_add_sphere.argtypes = [_P, _FP, _F, _I]
+        L.oracle_scene_set_sky.argtypes = [_P, ctypes.c_char_p]
+        L.oracle_scene_finish.argtypes = [_P]
+        L.oracle_max_depth_limit.argtypes = []
+        for f in (L.oracle_scene_add_material, L.oracle_scene_add_triangle, L.oracle_scene_add_quad, L.oracle_scene_add_sphere,
+                  L.oracle_scene_set_sky, L.oracle_scene_finish, L.oracle_max_depth_limit, L.oracle_render_pending):
+            f.restype = _I
+        L.oracle_render_pending.argtypes = [_P, _I, _I, _I, _I, _I, _U32, _P, _P, _P, _I, _I, _I, _P, _P]
         _oracle = L
     return _oracle
 
@@ -62,9 +77,42 @@ class OracleScene:
     WHICH = {"bunny": 0, "bunny4": 1, "plane1m": 2}
 
     def __init__(self, which="bunny", grid_n=708):
-        self.h = oracle().oracle_scene_create(self.WHICH[which], ASSETS.encode(), grid_n)
+        self.h = (oracle().oracle_scene_new() if which is None else
+                  oracle().oracle_scene_create(self.WHICH[which], ASSETS.encode(), grid_n))
         if not self.h:
             raise RuntimeError("oracle_scene_create failed")
+
+    # --- the builder: an empty scene (which=None), filled call by call, then finish() ---------------------
+    @staticmethod
+    def _f(v, n=3):
+        v = [float(x) for x in v]
+        assert len(v) == n
+        return (ctypes.c_float * n)(*v)
+
+    def add_material(self, fields16):
+        """The 16 floats of a GPUMaterial, every one as given; returns its index."""
+        i = oracle().oracle_scene_add_material(self.h, self._f(fields16, 16))
+        assert i >= 0, "oracle material table full"
+        return i
+
+    def add_triangle(self, a, b, c, material):
+        assert oracle().oracle_scene_add_triangle(self.h, self._f(a), self._f(b), self._f(c), material) == 0
+
+    def add_quad(self, a, b, c, d, material):
+        assert oracle().oracle_scene_add_quad(self.h, self._f(a), self._f(b), self._f(c), self._f(d), material) == 0
+
+    def add_sphere(self, position, radius, material):
+        assert oracle().oracle_scene_add_sphere(self.h, self._f(position), float(radius), material) == 0, "oracle sphere table full"
+
+    def set_sky(self, path):
+        assert oracle().oracle_scene_set_sky(self.h, path.encode() if path else None) == 0, f"cannot load sky {path}"
+
+    def set_camera(self, position, angle_x, angle_y):
+        oracle().oracle_set_camera(self.h, self._f(position), float(angle_x), float(angle_y))
+
+    def finish(self):
+        """Builds the BVH: 0, 1 (no triangles / bad call) or 2 (deeper than oracle_max_depth_limit(): never rendered)."""
+        return oracle().oracle_scene_finish(self.h)
 
     def __del__(self):
         if getattr(self, "h", None) and _oracle is not None:
@@ -96,6 +144,20 @@ class OracleScene:
         del keep
         assert code == 0
         return (out, st) if stats else out
+
+    def render_pending(self, w, h, spp, bounces, frame_index=0, seed=SEED, rng=None, last=None, threads=0):
+        """render() of a whole frame plus, per pixel, the largest number of pending entries the DFS stack held over
+        all of the pixel's rays (uint32 [h, w]); returns (frame, stats, pending), stats[7] the frame's maximum."""
+        out = np.zeros((h, w, 4), dtype=np.float32)
+        st = np.zeros(8, dtype=np.uint64)
+        pend = np.zeros((h, w), dtype=np.uint32)
+        rp = rng.ctypes.data if rng is not None else None
+        keep = np.ascontiguousarray(last, dtype=np.float32) if last is not None else None
+        code = oracle().oracle_render_pending(self.h, w, h, spp, bounces, frame_index, seed, rp,
+                                              keep.ctypes.data if keep is not None else None, out.ctypes.data, 0, h, threads,
+                                              st.ctypes.data, pend.ctypes.data)
+        assert code == 0, "oracle_render_pending refused the scene or the frame"
+        return out, st, pend
 
 
 def oracle_rng_state(seed, sub):
