@@ -115,6 +115,13 @@ class AoParams(ctypes.Structure):
                 ("scratch_bytes", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("waves_per_simd", ctypes.c_int32)]
 
 
+class RadianceParams(ctypes.Structure):
+    """rt_radiance_params (rt_abi.h)."""
+    _fields_ = [("rays", ctypes.c_void_p), ("count", ctypes.c_int64), ("rng", ctypes.c_void_p), ("radiance", ctypes.c_void_p),
+                ("bounces", ctypes.c_int32), ("samples", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("waves_per_simd", ctypes.c_int32)]
+
+
 class DenoiseParams(ctypes.Structure):
     """rt_denoise_params (rt_abi.h)."""
     _fields_ = [("surface", ctypes.c_void_p), ("pitch", ctypes.c_uint64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
@@ -147,6 +154,7 @@ REPROJECT_DEFAULT = -1  # RT_REPROJECT_DEFAULT: in a filter parameter of rt_repr
 # the defaults rt_reproject substitutes (csrc/reproject.hip; profiles/reproject_quality.txt)
 REPROJECT_DEFAULTS = {"max_history": 32, "sigma_plane": 0.03, "normal_min": 0.9}
 assert ctypes.sizeof(ReprojectParams) == 224 and ctypes.sizeof(GPUCamera) == 60
+assert ctypes.sizeof(RadianceParams) == 48
 
 # name -> (restype, argtypes); every symbol include/rt_abi.h declares.
 _P, _I, _U32, _U64, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_size_t
@@ -159,6 +167,7 @@ SIGNATURES = {
     "rt_occluded": (_I, [ctypes.POINTER(OcclusionParams), _P, _P]),
     "rt_ao_scratch_bytes": (_SZ, [_I, _I, _I]),
     "rt_ao": (_I, [ctypes.POINTER(AoParams), _P, _P]),
+    "rt_radiance": (_I, [ctypes.POINTER(RadianceParams), _P, _P]),
     "rt_denoise_scratch_bytes": (_SZ, [_I, _I]),
     "rt_denoise": (_I, [ctypes.POINTER(DenoiseParams), _P]),
     "rt_reproject": (_I, [ctypes.POINTER(ReprojectParams), _P]),
@@ -646,6 +655,77 @@ def occluded(scene, rays, out=None, stream=None, waves_per_simd=0):
     gpu = scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene)
     _check(lib().rt_occluded(ctypes.byref(p), ctypes.cast(gpu, ctypes.c_void_p), _stream_ptr(stream)), "rt_occluded")
     return out
+
+
+def radiance(scene, rays, rng, bounces=REFERENCE_BOUNCES, samples=1, out=None, stream=None, waves_per_simd=0):
+    """rt_radiance: the path-traced radiance along every ray of a float32 CUDA tensor [N, 8] (rt_ray rows, as
+    trace_rays takes them; tmax is not read) as a float32 [N, 4] tensor (`out`, or a new one): rgb = the mean of
+    `samples` evaluations of the reference's ray_color along the ray, w = 1.  `rng`: an int32 CUDA tensor of N states
+    (ray_rng, alloc_rng), state i read for ray i and written back advanced.  Pass unit directions unless the rays
+    reproduce the reference's camera (rt_abi.h).  Stream-ordered on `stream` (default: torch's current stream)."""
+    assert rays.dtype == torch.float32 and rays.is_cuda and rays.is_contiguous() and rays.dim() == 2 and rays.shape[1] == 8
+    n = rays.shape[0]
+    assert rng.dtype == torch.int32 and rng.is_cuda and rng.is_contiguous() and rng.numel() >= n * (RNG_STATE_BYTES // 4)
+    if out is None:
+        with _allocating_on(stream):
+            out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.dim() == 2
+    assert out.shape[1] == 4 and out.shape[0] >= n
+    if n == 0:  # rt_radiance returns at once for count 0; an empty tensor has no address to pass
+        return out
+    p = RadianceParams()
+    p.rays, p.count, p.rng, p.radiance = rays.data_ptr(), n, rng.data_ptr(), out.data_ptr()
+    p.bounces, p.samples = int(bounces), int(samples)
+    p.waves_per_simd = int(waves_per_simd)
+    gpu = scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene)
+    _check(lib().rt_radiance(ctypes.byref(p), ctypes.cast(gpu, ctypes.c_void_p), _stream_ptr(stream)), "rt_radiance")
+    return out
+
+
+def ray_rng(count, seed, device=None, stream=None):
+    """`count` RNG states for radiance(): state i is curand_init(seed, i, 0) (alloc_rng + rt_init_rng of a count x 1
+    frame), allocated and initialised on `stream` (default: torch's current stream)."""
+    with _allocating_on(stream):
+        rng = alloc_rng(int(count), device=device)
+    if int(count) > 0:
+        init_rng_states(rng, int(count), 1, seed, stream=stream)
+    return rng
+
+
+def panorama_rays(origin, width, height):
+    """A float32 [H*W, 8] numpy table of rt_ray rows: the equirectangular rays of a width x height panorama from
+    `origin`.  Row y*W + x, rows bottom to top like the surface: longitude phi = 2 pi (x + 0.5) / W - pi, latitude
+    theta = pi (y + 0.5) / H - pi / 2, direction (cos theta sin phi, sin theta, cos theta cos phi) -- the centre
+    column looks along +z, x grows to the right of it -- computed in float64 and rounded; tmax = RAY_TMAX.  (The
+    renderer's camera looking along +z has +x on its LEFT: shown as an image this map is the mirror image of what that
+    camera sees; flip the columns for a view from inside.)"""
+    w, h = int(width), int(height)
+    phi = 2.0 * np.pi * (np.arange(w, dtype=np.float64) + 0.5) / w - np.pi
+    theta = np.pi * (np.arange(h, dtype=np.float64) + 0.5) / h - 0.5 * np.pi
+    ct, st = np.cos(theta)[:, None], np.sin(theta)[:, None]
+    out = np.zeros((h, w, 8), dtype=np.float32)
+    out[..., 0:3] = np.asarray(origin, dtype=np.float32).reshape(3)
+    out[..., 3] = RAY_TMAX
+    out[..., 4], out[..., 5], out[..., 6] = ct * np.sin(phi)[None, :], st * np.ones((1, w)), ct * np.cos(phi)[None, :]
+    return out.reshape(h * w, 8)
+
+
+def panorama(scene, width, height, origin=None, samples=REFERENCE_SPP, bounces=REFERENCE_BOUNCES, seed=0xDEADBEEF,
+             device=None, stream=None):
+    """A width x height equirectangular panorama of an uploaded Scene seen from `origin` (default: its camera's
+    position) as a new pitched surface (alloc_surface layout, rows bottom to top): radiance() along panorama_rays()
+    with the states ray_rng(width * height, seed).  The rays are uploaded with a synchronous copy; the rest is
+    stream-ordered on `stream` (default: torch's current stream), where everything here is allocated."""
+    w, h = int(width), int(height)
+    if origin is None:
+        origin = tuple(scene.camera().origin)
+    with _allocating_on(stream):
+        rays = torch.from_numpy(panorama_rays(origin, w, h)).to(device or "cuda")
+        rng = ray_rng(w * h, seed, device=rays.device, stream=stream)
+        rgba = radiance(scene, rays, rng, bounces=bounces, samples=samples, stream=stream)
+        surface = alloc_surface(w, h, device=rays.device)
+        surface_view(surface, w).copy_(rgba.view(h, w, 4))
+    return surface
 
 
 def ao_directions(count=256):
@@ -1155,6 +1235,19 @@ class RayTracer:
             with _allocating_on(stream):
                 hits = trace_camera(self.scene, self.width, self.height, stream=stream)
         return ambient_occlusion(self.scene, hits, self.width, self.height, radius, **kw)
+
+    def panorama(self, width, height, origin=None, samples=None, bounces=None, seed=None, stream=None):
+        """A width x height equirectangular panorama of the scene seen from `origin` (default: the camera's position),
+        as a new pitched surface (alloc_surface layout, rows bottom to top): radiance() along panorama_rays(), `samples`
+        paths per pixel (default: spp), `bounces` (default: the tracer's), states ray_rng(width * height, seed) (default:
+        the tracer's seed).  Uploads the scene like process(); the frame index, the surfaces and the tracer's RNG states
+        are left alone."""
+        w, h = int(width), int(height)
+        self.scene.set_viewport(self.width, self.height)
+        self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
+        return panorama(self.scene, w, h, origin=origin, samples=self.spp if samples is None else samples,
+                        bounces=self.bounces if bounces is None else bounces, seed=self.seed if seed is None else seed,
+                        device=self.surface.device, stream=stream)
 
     def reprojected(self, **kw):
         """The current frame accumulated with the frames of earlier calls, whatever cameras they had (a lazily

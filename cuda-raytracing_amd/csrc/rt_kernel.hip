@@ -1085,6 +1085,75 @@ extern "C" int rt_ao(const rt_ao_params* p, const GPUScene* scene, void* stream)
     return check(launch_ao(v.stack, v.mode, w, a, (hipStream_t)stream), "ao_kernel launch");
 }
 
+// Radiance along the caller's rays (rt_abi.h): the checks that need no device first, then the scene's and the
+// buffers', then the radiance kernel (rt_radiance.hip) in rt_trace_rays' variant, on a RenderArgs filled as rt_render
+// fills it for a scene of its own.  Stream-ordered: no synchronisation, no allocation.
+// Default occupancy, the fastest measured (profiles/radiance_timing.txt, 2.07 M six-bounce paths): the lean MODE 17 at 7
+// waves per SIMD (config 2's scene 2.27-2.28 vs 2.28-2.31 / 2.32-2.37 ms at 6 / 5; the panorama 2.23 / 2.22 / 2.31); the
+// leaf-tree MODE 21 at 5, as the renderer and rt_trace_rays (config 4's scene 12.2-12.3 vs 15.8-16.1 / 17.9-18.3 ms at
+// 6 / 7, whose builds spill).  MODE 17 general has no benchmark scene: it follows the lean form.
+static int radiance_default_waves(const Variant& v) { return (v.mode & rtfast::TREE_BIT) ? 5 : 7; }
+
+extern "C" int rt_radiance(const rt_radiance_params* p, const GPUScene* scene, void* stream) {
+    if (!p) return set_error("rt_radiance: null params");
+    if (!scene) return set_error("rt_radiance: null scene");
+    if (!p->rays) return set_error("rt_radiance: null rays (there is no camera mode)");
+    if (!p->rng) return set_error("rt_radiance: null rng");
+    if (!p->radiance) return set_error("rt_radiance: null radiance");
+    if (p->flags != 0) return set_error("rt_radiance: flags must be 0");
+    if (p->waves_per_simd != 0 && (p->waves_per_simd < 5 || p->waves_per_simd > 7))
+        return set_error("rt_radiance: waves_per_simd must be 0 (default), 5, 6 or 7");
+    if (p->count < 0) return set_error("rt_radiance: negative count");
+    if (p->count > (int64_t)1 << 31) return set_error("rt_radiance: more than 2^31 rays in one call");
+    if (p->bounces < 0) return set_error("rt_radiance: bounces must be >= 0");
+    if (p->samples < 1 || p->samples > (1 << 24)) return set_error("rt_radiance: samples must be 1..2^24");
+    if ((((uintptr_t)p->rays) | ((uintptr_t)p->radiance)) & 15u)
+        return set_error("rt_radiance: rays and radiance must be 16-byte aligned");
+    if (((uintptr_t)p->rng) & 7u) return set_error("rt_radiance: rng must be 8-byte aligned");
+    if (p->count == 0) return 0;
+
+    QueryArgs q;
+    Variant v;
+    if (query_scene("rt_radiance", scene, &q, &v) != 0) return 1;
+    if (!scene->gpu_materials) return set_error("rt_radiance: the scene has no materials");
+    RadianceArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.r.spheres = q.spheres, a.r.sphere_count = q.sphere_count;
+    a.r.materials = scene->gpu_materials;
+    a.r.vertices = q.vertices, a.r.faces = q.faces;
+    a.r.nodes = q.nodes, a.r.tris = q.tris;
+    a.r.pairs = q.pairs, a.r.quads = q.quads, a.r.units = q.units, a.r.tree = q.tree, a.r.ltris = q.ltris;
+    a.r.spairs = q.spairs, a.r.flat = q.flat, a.r.face_leaf = q.face_leaf;
+    a.r.scene_fast = q.scene_fast;
+    if (scene->environment_cubemap_tex) {
+        const int n = cube_size(scene->environment_cubemap_tex);
+        if (n <= 0) return set_error("rt_radiance: unknown environment cube map handle");
+        a.r.sky = (const float*)scene->environment_cubemap_tex;
+        a.r.sky_n = n;
+    }
+    sky_quat(&a.r.qw, &a.r.qx, &a.r.qy, &a.r.qz);
+    a.r.bounces = p->bounces;
+    // a short buffer would fault the GPU
+    const size_t n = (size_t)p->count;
+    if (bytes_from(p->rays) < n * sizeof(rt_ray)) return set_error("rt_radiance: rays too small");
+    if (bytes_from(p->rng) < n * sizeof(rt_rng_state)) return set_error("rt_radiance: rng too small");
+    if (bytes_from(p->radiance) < n * 16) return set_error("rt_radiance: radiance too small");
+    // a lane re-reads its ray per sample and its state at the start: an output row written over either would change them
+    auto overlaps = [&](const void* b, size_t bytes) {
+        const uintptr_t o = (uintptr_t)p->radiance, x = (uintptr_t)b;
+        return o < x + bytes && x < o + n * 16;
+    };
+    if (overlaps(p->rays, n * sizeof(rt_ray))) return set_error("rt_radiance: radiance overlaps rays");
+    if (overlaps(p->rng, n * sizeof(rt_rng_state))) return set_error("rt_radiance: radiance overlaps rng");
+    a.rays = p->rays;
+    a.rng = p->rng;
+    a.radiance = (float4*)p->radiance;
+    a.count = p->count;
+    a.samples = p->samples;
+    const int w = p->waves_per_simd ? p->waves_per_simd : radiance_default_waves(v);
+    return check(launch_radiance(v.stack, v.mode, w, a, (hipStream_t)stream), "radiance_kernel launch");
+}
+
 // 1 when librt_hip_exp.so's render paths are registered (rt_render.h ExperimentalKernels).
 extern "C" int rt_experimental_loaded() { return rtk::experimental_kernels() ? 1 : 0; }
 

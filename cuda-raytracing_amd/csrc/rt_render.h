@@ -83,6 +83,22 @@ struct AoArgs {
 hipError_t launch_occlusion(int stack, int mode, int waves_per_simd, const OcclusionArgs& a, hipStream_t s);
 hipError_t launch_ao(int stack, int mode, int waves_per_simd, const AoArgs& a, hipStream_t s);
 
+// The radiance kernel (rt_radiance.hip, rt_radiance): render_fast_body's per-lane sample state machine over a ray
+// list, the query kernel's variants.  The kernel's only parameter begins with a RenderArgs, so shade_segment
+// (rt_fast_body.h) runs on it unchanged and its COLD reads from the kernel-argument segment find their fields:
+// `r` holds what rt_render fills for a scene of its own -- the shading arrays, the sky, the mirror, bounces -- and
+// zero everywhere else (no camera, surface, RNG array, tile list, lane map, gate, statistics; tune 0).
+struct RadianceArgs {
+    RenderArgs r;
+    const rt_ray* rays;
+    rt_rng_state* rng;  // state i for ray i
+    float4* radiance;
+    long long count;
+    int samples;
+};
+static_assert(offsetof(RadianceArgs, r) == 0, "the kernel-argument segment starts with the RenderArgs");
+hipError_t launch_radiance(int stack, int mode, int waves_per_simd, const RadianceArgs& a, hipStream_t s);
+
 // In librt_hip_exp.so beside its families:
 // The lone-pixel kernel (rt_lone.hip): one wave per slot of `lone_slots`, through the treelets.
 hipError_t launch_lone(const RenderArgs& a, const int32_t* lone_slots, int lone_count, const void* treelets, hipStream_t s);

@@ -452,6 +452,58 @@ size_t rt_ao_scratch_bytes(int width, int height, int samples);
 int rt_ao(const rt_ao_params* params, const GPUScene* scene, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Radiance along caller-given rays: the renderer's path tracing without its camera and its pixel grid
+ * (environment probes and panoramas, fisheye or stereo cameras, depth of field, light-map texels,
+ * irradiance probes, a second view of the same scene).
+ *
+ * radiance[i].rgb is the fp32 mean of `samples` evaluations of the reference's
+ * ray_color(origin_i, direction_i, rng_i, bounces) (main_raytracing.cu:111-158: emission, the
+ * specular / diffuse lobe from 4 draws per hit, Russian roulette, the sky on a miss), accumulated in
+ * sample order and divided by (float)samples as the renderer divides by its sample count; w = 1.  State i
+ * is read, advances through all the samples (4 draws per hit, none on a miss) and is written back.
+ *
+ * There is no jitter and no camera: every sample starts along the same ray.  The direction is used as
+ * given for the first segment, exactly as the renderer uses its unnormalised camera direction: the
+ * traversal and the hit point take normalize(direction), the first hit's reflect() takes the vector as
+ * given.  PASS UNIT DIRECTIONS unless you reproduce the reference's camera (a ray that is the renderer's
+ * jittered camera ray, with the state advanced past the two jitter draws, gives the renderer's sample bit
+ * for bit).  Every segment, the first included, is bounded by the renderer's 1e30f: rt_ray.tmax and
+ * rt_ray.reserved are not read.  The sky is the scene's cube map under the renderer's rotation.
+ *
+ * bounces == 0 gives (0, 0, 0, 1) and leaves the states untouched.  A ray whose normalised direction has
+ * a non-finite component (a zero, infinite or NaN direction) is not traced: it gives (0, 0, 0, 1) and its
+ * state is unchanged.  A non-finite origin is traced as rt_trace_rays traces it.
+ * ------------------------------------------------------------------------------------- */
+typedef struct rt_radiance_params {
+    const rt_ray* rays;      /* DEVICE, count records, 16-byte aligned; tmax and the reserved word are not read */
+    int64_t count;           /* 0 returns at once; at most 2^31 */
+    rt_rng_state* rng;       /* DEVICE, count states, 8-byte aligned: state i is read for ray i and written back */
+    float* radiance;         /* DEVICE, count float4, 16-byte aligned: rgb, w = 1; rows at and past count untouched */
+    int32_t bounces;         /* >= 0 */
+    int32_t samples;         /* 1 .. 2^24: paths per ray, along the same ray */
+    uint32_t flags;          /* must be 0 */
+    int32_t waves_per_simd;  /* occupancy build of the kernel: 5 / 6 / 7, or 0 = the default
+                                (profiles/radiance_timing.txt) */
+} rt_radiance_params;        /* 48 B */
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_radiance_params) == 48 && offsetof(rt_radiance_params, rays) == 0 &&
+              offsetof(rt_radiance_params, count) == 8 && offsetof(rt_radiance_params, rng) == 16 &&
+              offsetof(rt_radiance_params, radiance) == 24 && offsetof(rt_radiance_params, bounces) == 32 &&
+              offsetof(rt_radiance_params, samples) == 36 && offsetof(rt_radiance_params, flags) == 40 &&
+              offsetof(rt_radiance_params, waves_per_simd) == 44,
+              "rt_radiance_params");
+#endif
+
+/* Radiance of a batch on `stream` (a hipStream_t, NULL = null stream): stream-ordered, no synchronisation, no
+ * allocation, one kernel launch.  The scene rules are rt_trace_rays': uploaded by rt_scene_upload (its own
+ * rng_state is not used here and may be NULL), a GPUScene filled by another host is rejected.  The arguments
+ * that need no device are checked first (NULL params, scene, rays, rng or radiance; flags; waves_per_simd;
+ * count < 0 or > 2^31; bounces; samples; alignment), then the scene, then the buffer sizes; `radiance` may not
+ * overlap `rays` or `rng`.  Returns 0 or an error code with rt_last_error(). */
+int rt_radiance(const rt_radiance_params* params, const GPUScene* scene, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Denoising: a viewable image from one low-sample frame and the first-hit records of its camera
  * (render -> rt_trace_rays in camera mode -> rt_denoise).  An edge-avoiding a-trous wavelet filter on
  * the frame divided by the first hit's albedo, guided by normal, position and distance; the albedo
@@ -788,7 +840,7 @@ int rt_scene_setup_plane(rt_scene* scene, int n, const char* assets_dir);
 size_t rt_scene_host_arrays(const rt_scene* scene, const GPUBVHNode** nodes, size_t* node_count,
                             const uint32_t** face_indices, size_t* face_count, const GPUVertex** vertices,
                             size_t* vertex_count, const GPUFace** faces);
-/* The BVH's depth.  rt_render, rt_trace_rays, rt_occluded and rt_ao refuse a scene deeper than 62 levels (the
+/* The BVH's depth.  rt_render, rt_trace_rays, rt_occluded, rt_ao and rt_radiance refuse a scene deeper than 62 levels (the
  * traversal stacks hold depth + 2 <= 64 entries; csrc/rt_variant.h kMaxBvhDepth) with an error that names the limit,
  * before anything is launched.  rt_scene_upload refuses a scene without triangles. */
 int rt_scene_bvh_max_depth(const rt_scene* scene);

@@ -6,6 +6,7 @@
     python tools/render_image.py --denoise
     python tools/render_image.py --ao RADIUS
     python tools/render_image.py --temporal K
+    python tools/render_image.py --panorama W
 
 --aov PREFIX also writes the first-hit images of the same camera (rt.gbuffer: pixel centres, no jitter) as
 PREFIX_normal.pfm (normal * 0.5 + 0.5), PREFIX_depth.pfm (hit distance, inf on a miss) and PREFIX_albedo.pfm.
@@ -15,6 +16,8 @@ same camera's first-hit records, into a surface of its own (the progressive hist
 first-hit records, 8 samples per pixel of length RADIUS (1 = open, 0 = closed, 1 where the camera ray missed).
 --temporal K also writes OUT_temporal.pfm / .ppm: K frames of the config's spp, each rendered with frame_index 0 along a
 small camera dolly that ends at the config's camera, accumulated by rt.TemporalAccumulator (rt_reproject).
+--panorama W also writes OUT_panorama.pfm / .ppm: the W x W/2 equirectangular panorama of the scene from the camera's
+position at the config's spp and bounces (rt.panorama: rt_radiance along rt.panorama_rays).
 """
 import argparse
 import os
@@ -47,6 +50,7 @@ def main():
     ap.add_argument("--denoise", action="store_true")
     ap.add_argument("--ao", type=float, default=None, metavar="RADIUS")
     ap.add_argument("--temporal", type=int, default=None, metavar="K")
+    ap.add_argument("--panorama", type=int, default=None, metavar="W")
     args = ap.parse_args()
     rt = G.load_package()
     scene_name, W, H, SPP, BOUNCES, _ = bench.CONFIGS[args.config]
@@ -90,6 +94,13 @@ def main():
         rt.write_ppm(args.out + "_temporal.ppm", rt.tonemap(moving, W, H))
         print(f"wrote {args.out}_temporal.pfm / .ppm ({args.temporal} frames x {SPP} spp along a dolly; "
               f"mean history {float(acc.history.mean()):.1f} frames)")
+    if args.panorama is not None:
+        pw, ph = args.panorama, args.panorama // 2
+        assert pw >= 2
+        pano = rt.panorama(scene, pw, ph, samples=SPP, bounces=BOUNCES, seed=bench.SEED)
+        rt.write_pfm(args.out + "_panorama.pfm", pano, pw, ph)
+        rt.write_ppm(args.out + "_panorama.ppm", rt.tonemap(pano, pw, ph))
+        print(f"wrote {args.out}_panorama.pfm / .ppm ({pw}x{ph} equirectangular from the camera's position, {SPP} spp)")
     if args.aov:
         g = rt.gbuffer(scene, W, H)
         images = {"normal": g["normal"] * 0.5 + 0.5,
