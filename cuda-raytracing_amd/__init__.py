@@ -141,6 +141,24 @@ class ReprojectParams(ctypes.Structure):
                 ("sigma_plane", ctypes.c_float), ("normal_min", ctypes.c_float), ("flags", ctypes.c_int32)]
 
 
+class MomentsParams(ctypes.Structure):
+    """rt_moments_params (rt_abi.h)."""
+    _fields_ = [("surface", ctypes.c_void_p), ("pitch", ctypes.c_uint64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("hits", ctypes.c_void_p), ("materials", ctypes.c_void_p), ("material_count", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("out", ctypes.c_void_p), ("out_pitch", ctypes.c_uint64)]
+
+
+class DenoiseVarianceParams(ctypes.Structure):
+    """rt_denoise_variance_params (rt_abi.h)."""
+    _fields_ = [("surface", ctypes.c_void_p), ("pitch", ctypes.c_uint64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("hits", ctypes.c_void_p), ("materials", ctypes.c_void_p), ("material_count", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("moments", ctypes.c_void_p), ("moments_pitch", ctypes.c_uint64),
+                ("history", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_pitch", ctypes.c_uint64),
+                ("out_variance", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_uint64),
+                ("iterations", ctypes.c_int32), ("normal_power_log2", ctypes.c_int32), ("sigma_plane", ctypes.c_float),
+                ("sigma_lum", ctypes.c_float), ("min_history", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
 HIT_MISS, HIT_SPHERE, HIT_TRIANGLE = 0, 1, 2  # rt_hit.kind
 RAY_TMAX = 1e30  # the renderer's own initial closest distance (main_raytracing.cu:85)
 DENOISE_DEFAULT = -1  # RT_DENOISE_DEFAULT: in a filter parameter of rt_denoise, the measured default
@@ -155,6 +173,9 @@ REPROJECT_DEFAULT = -1  # RT_REPROJECT_DEFAULT: in a filter parameter of rt_repr
 REPROJECT_DEFAULTS = {"max_history": 32, "sigma_plane": 0.03, "normal_min": 0.9}
 assert ctypes.sizeof(ReprojectParams) == 224 and ctypes.sizeof(GPUCamera) == 60
 assert ctypes.sizeof(RadianceParams) == 48
+# the defaults rt_denoise_variance substitutes (csrc/denoise_variance.hip; profiles/variance_quality.txt)
+DENOISE_VARIANCE_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_plane": 0.03, "sigma_lum": 4.0, "min_history": 4.0}
+assert ctypes.sizeof(MomentsParams) == 64 and ctypes.sizeof(DenoiseVarianceParams) == 136
 
 # name -> (restype, argtypes); every symbol include/rt_abi.h declares.
 _P, _I, _U32, _U64, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_size_t
@@ -171,6 +192,9 @@ SIGNATURES = {
     "rt_denoise_scratch_bytes": (_SZ, [_I, _I]),
     "rt_denoise": (_I, [ctypes.POINTER(DenoiseParams), _P]),
     "rt_reproject": (_I, [ctypes.POINTER(ReprojectParams), _P]),
+    "rt_moments": (_I, [ctypes.POINTER(MomentsParams), _P]),
+    "rt_denoise_variance_scratch_bytes": (_SZ, [_I, _I]),
+    "rt_denoise_variance": (_I, [ctypes.POINTER(DenoiseVarianceParams), _P]),
     "rt_foreign_mirror_wait": (_I, [_P]),
     "rt_foreign_last_tracer": (_I, [_P]),
     "rt_experimental_loaded": (_I, []),
@@ -980,6 +1004,184 @@ class TemporalAccumulator:
         return None if self._latest is None else self._slots[self._latest][2]
 
 
+def _materials_of(scene_or_materials):
+    """(device pointer or None, count) of a Scene's, a GPUScene's or a float32 CUDA [M, 16] tensor's material table."""
+    m = scene_or_materials
+    if isinstance(m, torch.Tensor):
+        assert m.dtype == torch.float32 and m.is_cuda and m.is_contiguous() and m.dim() == 2 and m.shape[1] == 16
+        return (m.data_ptr() if m.shape[0] else None), m.shape[0]
+    gpu = m.gpu.contents if hasattr(m, "gpu") else m
+    return gpu.gpu_materials, gpu.material_count
+
+
+def moments(scene_or_materials, surface, hits, width, height, out=None, stream=None):
+    """rt_moments: the luminance moments (l, l*l, 0, alpha) of one frame, `surface`, divided by its first hits'
+    albedo, as a pitched float4 surface -- what a second rt_reproject accumulates for rt_denoise_variance.
+    `scene_or_materials`: an uploaded Scene (or GPUScene), or a float32 CUDA tensor [M, 16] of GPUMaterial rows.
+    Returns `out` (a new surface when None; `out is surface` is refused).  Stream-ordered on `stream` (default:
+    torch's current stream); a surface allocated here is allocated on that stream."""
+    w, h = int(width), int(height)
+    assert _is_surface(surface, w, h) and _is_hits(hits, w, h)
+    with _allocating_on(stream):
+        if out is None:
+            out = alloc_surface(w, h, device=surface.device)
+    assert _is_surface(out, w, h)
+    p = MomentsParams()
+    p.surface, p.pitch, p.width, p.height = surface.data_ptr(), surface.stride(0) * 4, w, h
+    p.hits = hits.data_ptr()
+    p.materials, p.material_count = _materials_of(scene_or_materials)
+    p.out, p.out_pitch = out.data_ptr(), out.stride(0) * 4
+    _check(lib().rt_moments(ctypes.byref(p), _stream_ptr(stream)), "rt_moments")
+    return out
+
+
+def denoise_variance_scratch_bytes(width, height):
+    """rt_denoise_variance_scratch_bytes: bytes of scratch rt_denoise_variance needs for a width x height frame."""
+    return int(lib().rt_denoise_variance_scratch_bytes(int(width), int(height)))
+
+
+def _denoise_variance(surface, hits, materials, width, height, moments, history, out, out_variance, scratch, iterations,
+                      normal_power_log2, sigma_plane, sigma_lum, min_history, stream):
+    w, h = int(width), int(height)
+    assert _is_surface(surface, w, h) and _is_hits(hits, w, h)
+    assert moments is None or _is_surface(moments, w, h)
+    assert history is None or _is_history(history, w, h)
+    need = denoise_variance_scratch_bytes(w, h)
+    # allocated on the stream the kernels run on, as in _denoise
+    with _allocating_on(stream):
+        if out is None:
+            out = alloc_surface(w, h, device=surface.device)
+        if out_variance is None:
+            out_variance = torch.zeros((h, w), dtype=torch.float32, device=surface.device)
+        if scratch is None:
+            scratch = torch.empty((need // 4,), dtype=torch.float32, device=surface.device)
+    assert _is_surface(out, w, h) and _is_history(out_variance, w, h)
+    assert scratch.is_cuda and scratch.is_contiguous()
+    p = DenoiseVarianceParams()
+    p.surface, p.pitch, p.width, p.height = surface.data_ptr(), surface.stride(0) * 4, w, h
+    p.hits = hits.data_ptr()
+    p.materials, p.material_count = _materials_of(materials)
+    if moments is not None:
+        p.moments, p.moments_pitch = moments.data_ptr(), moments.stride(0) * 4
+    if history is not None:
+        p.history = history.data_ptr()
+    p.out, p.out_pitch, p.out_variance = out.data_ptr(), out.stride(0) * 4, out_variance.data_ptr()
+    p.scratch, p.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
+    p.iterations, p.normal_power_log2 = int(iterations), int(normal_power_log2)
+    p.sigma_plane, p.sigma_lum, p.min_history = float(sigma_plane), float(sigma_lum), float(min_history)
+    _check(lib().rt_denoise_variance(ctypes.byref(p), _stream_ptr(stream)), "rt_denoise_variance")
+    return out, out_variance
+
+
+def denoise_variance_raw(surface, hits, materials, width, height, moments=None, history=None, out=None, out_variance=None,
+                         scratch=None, iterations=DENOISE_DEFAULT, normal_power_log2=DENOISE_DEFAULT,
+                         sigma_plane=DENOISE_DEFAULT, sigma_lum=DENOISE_DEFAULT, min_history=DENOISE_DEFAULT, stream=None):
+    """rt_denoise_variance on tensors only: `surface` the accumulated image (a pitched float4 surface), `hits` the
+    float32 [H*W, 12] records of trace_camera, `materials` a float32 CUDA tensor [M, 16] of GPUMaterial rows (M may
+    be 0), `moments` the accumulated moments surface (moments() through reproject_raw) and `history` the colour's
+    float32 [H, W] history, either or both None.  Returns (out, out_variance): the filtered surface (`out is surface`
+    is allowed) and the float32 [H, W] filtered variance of the albedo-divided luminance (new tensors when None).
+    `scratch`: any contiguous CUDA tensor of at least denoise_variance_scratch_bytes(width, height) bytes.  A filter
+    parameter left at DENOISE_DEFAULT takes the library's default (DENOISE_VARIANCE_DEFAULTS).  Stream-ordered on
+    `stream` (default: torch's current stream); tensors allocated here are allocated on that stream, tensors passed
+    in must be safe to use on it."""
+    assert isinstance(materials, torch.Tensor)
+    return _denoise_variance(surface, hits, materials, width, height, moments, history, out, out_variance, scratch,
+                             iterations, normal_power_log2, sigma_plane, sigma_lum, min_history, stream)
+
+
+def denoise_variance(scene, surface, width, height, hits=None, moments=None, history=None, out=None, out_variance=None,
+                     scratch=None, iterations=DENOISE_DEFAULT, normal_power_log2=DENOISE_DEFAULT,
+                     sigma_plane=DENOISE_DEFAULT, sigma_lum=DENOISE_DEFAULT, min_history=DENOISE_DEFAULT, stream=None):
+    """rt_denoise_variance for an uploaded Scene: guided by the camera's first-hit records (`hits`, or
+    trace_camera(scene, width, height) when None) and the scene's materials; otherwise denoise_variance_raw.  Feed it
+    the accumulated image with the history and moments that belong to it (VarianceAccumulator does all of it)."""
+    if hits is None:
+        with _allocating_on(stream):
+            hits = trace_camera(scene, width, height, stream=stream)
+    return _denoise_variance(surface, hits, scene, width, height, moments, history, out, out_variance, scratch,
+                             iterations, normal_power_log2, sigma_plane, sigma_lum, min_history, stream)
+
+
+class VarianceAccumulator:
+    """The per-frame chain of the variance-steered filter: rt_reproject on the colour (a TemporalAccumulator),
+    rt_moments on the new frame, rt_reproject on the moments with a history of their own, rt_denoise_variance on
+    the accumulated image.  **filter_params are denoise_variance_raw's iterations, normal_power_log2, sigma_plane,
+    sigma_lum and min_history; `reproject_params` (a dict) are reproject_raw's max_history, sigma_plane and
+    normal_min, used for both reprojections.  Static geometry only."""
+
+    def __init__(self, width, height, reproject_params=None, **filter_params):
+        unknown = set(filter_params) - set(DENOISE_VARIANCE_DEFAULTS)
+        assert not unknown, sorted(unknown)
+        self.width, self.height = int(width), int(height)
+        self.filter_params = dict(filter_params)
+        self._colour = TemporalAccumulator(width, height, **(reproject_params or {}))
+        self._moment_slots = [None, None]  # (accumulated moments, their history)
+        self._buffers = None               # (moments of the frame, filtered image, variance, scratch)
+        self.reset()
+
+    @property
+    def reproject_params(self):
+        return self._colour.filter_params
+
+    def reset(self):
+        """Forget the history: the next push starts a new accumulation."""
+        self._colour.reset()
+        self._pushed = False
+
+    def push(self, scene, surface, hits=None, stream=None):
+        """Accumulate `surface`, a frame of the uploaded `scene`'s current camera rendered with frame_index 0, and
+        filter the accumulated image; `hits`: that camera's trace_camera records (traced here when None).  Returns
+        the filtered surface, valid until the next push."""
+        w, h = self.width, self.height
+        before, prev_camera = self._colour._latest, self._colour._camera
+        accumulated = self._colour.push(scene, surface, hits=hits, stream=stream)
+        k = self._colour._latest
+        _, own_hits, history = self._colour._slots[k]
+        with _allocating_on(stream):
+            if self._moment_slots[k] is None:
+                self._moment_slots[k] = (alloc_surface(w, h, device=surface.device),
+                                         torch.zeros((h, w), dtype=torch.float32, device=surface.device))
+            if self._buffers is None:
+                self._buffers = (alloc_surface(w, h, device=surface.device), alloc_surface(w, h, device=surface.device),
+                                 torch.zeros((h, w), dtype=torch.float32, device=surface.device),
+                                 torch.empty((denoise_variance_scratch_bytes(w, h) // 4,), dtype=torch.float32,
+                                             device=surface.device))
+        frame_moments, filtered, variance, scratch = self._buffers
+        moments(scene, surface, own_hits, w, h, out=frame_moments, stream=stream)
+        prev = None
+        if before is not None:
+            prev = (self._moment_slots[before][0], self._colour._slots[before][1], self._moment_slots[before][1], prev_camera)
+        acc_moments, moments_history = self._moment_slots[k]
+        reproject_raw(frame_moments, own_hits, self._colour._camera, w, h, prev=prev, out=acc_moments,
+                      out_history=moments_history, stream=stream, **self._colour.filter_params)
+        _denoise_variance(accumulated, own_hits, scene, w, h, acc_moments, history, filtered, variance, scratch,
+                          stream=stream, **{**{k_: DENOISE_DEFAULT for k_ in DENOISE_VARIANCE_DEFAULTS}, **self.filter_params})
+        self._pushed = True
+        return filtered
+
+    @property
+    def accumulated(self):
+        """The latest accumulated (unfiltered) surface (None before the first push)."""
+        return None if not self._pushed else self._colour._slots[self._colour._latest][0]
+
+    @property
+    def history(self):
+        """[H, W]: the number of frames the accumulated surface holds per pixel (None before the first push)."""
+        return None if not self._pushed else self._colour.history
+
+    @property
+    def moments(self):
+        """The latest accumulated moments surface (None before the first push)."""
+        return None if not self._pushed else self._moment_slots[self._colour._latest][0]
+
+    @property
+    def variance(self):
+        """[H, W]: the filtered variance of the albedo-divided luminance of the latest filtered image (None before
+        the first push)."""
+        return None if not self._pushed else self._buffers[2]
+
+
 def foreign_mirror_wait(gpu_scene):
     """rt_foreign_mirror_wait: block until the background mirror build of a foreign GPUScene (a
     ctypes GPUScene filled by the caller) has finished; the next render installs it."""
@@ -1194,6 +1396,7 @@ class RayTracer:
         self.rng = None
         self.frame_index = 0
         self._accumulator = None
+        self._variance_accumulator = None
 
     def process(self, stats=None):
         if self.rng is None:
@@ -1264,6 +1467,30 @@ class RayTracer:
         assert not set(kw) - set(REPROJECT_DEFAULTS), sorted(set(kw) - set(REPROJECT_DEFAULTS))
         self._accumulator.filter_params.update(kw)
         return self._accumulator.push(self.scene, self.surface, **push_kw)
+
+    def filtered(self, **kw):
+        """The current frame accumulated with the frames of earlier calls and filtered by rt_denoise_variance (a
+        lazily created VarianceAccumulator, kept apart from reprojected()'s accumulator; **kw are its filter
+        parameters, `reproject_params`, and push's hits and stream).  Meant for frames rendered with frame_index == 0,
+        like reprojected().  Returns the filtered surface, valid until the next call; the accumulator itself
+        (accumulated image, history, variance) is `tracer.variance_accumulator`.  Uploads the scene like process();
+        `surface`, `last_frame`, the RNG states and the frame index are left alone.  on_resize drops the accumulator."""
+        self.scene.set_viewport(self.width, self.height)
+        self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
+        push_kw = {k: kw.pop(k) for k in ("hits", "stream") if k in kw}
+        reproject_params = kw.pop("reproject_params", None)
+        acc = self.variance_accumulator
+        if acc is None or (acc.width, acc.height) != (self.width, self.height):
+            acc = self._variance_accumulator = VarianceAccumulator(self.width, self.height)
+        assert not set(kw) - set(DENOISE_VARIANCE_DEFAULTS), sorted(set(kw) - set(DENOISE_VARIANCE_DEFAULTS))
+        acc.filter_params.update(kw)
+        acc.reproject_params.update(reproject_params or {})
+        return acc.push(self.scene, self.surface, **push_kw)
+
+    @property
+    def variance_accumulator(self):
+        """filtered()'s VarianceAccumulator (None before the first call and after on_resize)."""
+        return getattr(self, "_variance_accumulator", None)
 
     def save(self, path):
         """The current frame: ``.pfm`` linear RGB, ``.ppm`` as the reference's viewer shows it

@@ -673,6 +673,144 @@ static_assert(sizeof(rt_reproject_params) == 224 && offsetof(rt_reproject_params
  * are refused: other lanes gather from them.  Returns 0 or an error code with rt_last_error(). */
 int rt_reproject(const rt_reproject_params* params, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Variance-steered denoising: rt_denoise's filter with a colour tolerance of its own for every pixel, set by
+ * an estimate of the variance of the pixel's luminance as stored -- small where rt_reproject's running mean
+ * holds many frames, large where a pixel was just disoccluded -- and filtered along with the colours (the
+ * spatial half of SVGF).  Per frame:
+ *
+ *   render with frame_index 0 -> rt_trace_rays in camera mode
+ *     -> rt_reproject (the colour)               -> accumulated image A, history Hc
+ *     -> rt_moments (the new frame)              -> moments surface M
+ *     -> rt_reproject (M, with its own prev_surface and prev_history, the same hits, prev_hits and cameras)
+ *                                                -> accumulated moments AM
+ *     -> rt_denoise_variance(A, AM, Hc)          -> the filtered image, and the variance image
+ *
+ * The temporal accumulation of the moments is rt_reproject itself: its running mean of (l, l*l) is the first and
+ * second moment.  There is no second reprojection kernel.
+ *
+ * The arithmetic is fixed as rt_denoise's is (fp32, no contraction, IEEE division, only + - * /, fmaxf, fabsf and
+ * comparisons; no exp and no sqrt: the tolerance is used squared), so that tests/variance_ref.py restates both
+ * calls bit for bit.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, lum(c) = (0.2126f*c.x + 0.7152f*c.y) + 0.0722f*c.z.
+ * valid(p), the albedo a_p with its 2^-6 floor and the weights wn and wz (with normal_power_log2 and
+ * sigma_plane * t_p) are exactly rt_denoise's (steps 1 and 2 of its block above).
+ *
+ * rt_moments, per pixel p: c = surface.rgb / a_p, l = lum(c), out = (l, l*l, 0, surface.a).  A c that is not finite
+ * gives moments that are not finite, on purpose: rt_reproject's rules 4 and 5 then heal or isolate that pixel
+ * exactly as they do for the colour.
+ *
+ * rt_denoise_variance:
+ *  1. Prepare.  c_p = surface.rgb / a_p; alpha passes through untouched.  The initial variance v_p estimates the
+ *     variance of lum(c_p) as stored, that is, of the accumulated value.  hist = history[p], or 1 when history is
+ *     NULL; (m1, m2) = moments[p].xy.
+ *       !valid(p) or c_p.rgb not finite: v_p = 0.
+ *       else, temporal, when moments != NULL, hist >= min_history (false for a NaN) and m1 and m2 are finite:
+ *         v_p = fmaxf(0, m2 - m1*m1) / fmaxf(hist, 1.0f).
+ *       else, spatial: s1 = s2 = ws = 0; for dy = -3..3 (outer), dx = -3..3 (inner), q = (x + dx, y + dy) inside
+ *         the image with valid(q) and c_q.rgb finite (p itself is one of them): w = wn * wz (no kernel weight);
+ *         if w > 0: s1 += lum(c_q) * w, s2 += (lum(c_q) * lum(c_q)) * w, ws += w.
+ *         v_p = ws > 0 ? fmaxf(0, s2 / ws - (s1 / ws) * (s1 / ws)) : 0.
+ *  2. `iterations` passes s = 0.., step = 1 << s, each from the previous pass's colours and variances.  !valid(p)
+ *     keeps c_p and v_p.  Otherwise:
+ *       prefilter: vsum = ksum = 0; for dy = -1..1 (outer), dx = -1..1 (inner), q = (x + dx, y + dy) -- stride 1
+ *         whatever the pass -- inside the image with valid(q): k = kp[dy+1] * kp[dx+1], kp = {1/4, 1/2, 1/4};
+ *         vsum += v_q * k, ksum += k.  vg = vsum / ksum (p itself is always taken).
+ *       tol = (sigma_lum * sigma_lum) * vg + 1e-8f.
+ *       the 25 taps of rt_denoise's step 2 in its order and with its skips (q outside the image, !valid(q), c_q.rgb
+ *         not finite), q = (x + dx*step, y + dy*step):
+ *         wl = 1 / (1 + (d * d) / tol) with d = lum(c_q) - lum(c_p) when c_p.rgb is finite, else 1;
+ *         w = (((h[dy+2] * h[dx+2]) * wn) * wz) * wl;
+ *         if w > 0: sum += c_q * w, vs += v_q * (w * w), wsum += w.
+ *       c' = wsum > 0 ? sum / wsum : c_p.   v' = wsum > 0 ? vs / (wsum * wsum) : v_p.
+ *  3. out.rgb = c * a_p, out.a = surface.a, out_variance[p] = v_p (0 for !valid(p)).  Row padding of `out` is
+ *     never written, nor anything past width * height floats of out_variance.
+ *
+ * The variance is that of the albedo-divided luminance: multiply by lum(a_p)^2 for an estimate in the image's units.
+ *
+ * PITFALL: feed rt_denoise_variance the *accumulated* image with the history and moments that belong to it, and
+ * render the frames with frame_index 0 (rt_reproject's pitfall): the temporal estimate divides the moments'
+ * variance by the history length, which is the variance of the running mean only for the image that mean made.
+ * ------------------------------------------------------------------------------------- */
+typedef struct rt_moments_params {
+    const void* surface;           /* DEVICE pitched float4: the new frame (not the accumulated image) */
+    uint64_t pitch;                /* bytes per row: >= width * 16, a multiple of 16 (both pitches) */
+    int32_t width, height;         /* > 0; height <= RT_DENOISE_MAX_HEIGHT, width * height <= RT_DENOISE_MAX_PIXELS */
+    const rt_hit* hits;            /* DEVICE width * height records of rt_trace_rays' camera mode */
+    const GPUMaterial* materials;  /* DEVICE (GPUScene.gpu_materials); may be NULL when material_count is 0 */
+    int32_t material_count;
+    int32_t flags;                 /* must be 0 */
+    void* out;                     /* DEVICE pitched float4 (l, l*l, 0, alpha); must not overlap surface or hits */
+    uint64_t out_pitch;
+} rt_moments_params;
+
+typedef struct rt_denoise_variance_params {
+    const void* surface;           /* DEVICE pitched float4: the accumulated image (rt_reproject's out) */
+    uint64_t pitch;                /* bytes per row: >= width * 16, a multiple of 16 (all three pitches) */
+    int32_t width, height;         /* > 0; height <= RT_DENOISE_MAX_HEIGHT, width * height <= RT_DENOISE_MAX_PIXELS */
+    const rt_hit* hits;            /* DEVICE width * height records of rt_trace_rays' camera mode */
+    const GPUMaterial* materials;  /* DEVICE (GPUScene.gpu_materials); may be NULL when material_count is 0 */
+    int32_t material_count;
+    int32_t flags;                 /* must be 0 */
+    const void* moments;           /* DEVICE pitched float4: the accumulated moments; NULL = spatial estimate everywhere */
+    uint64_t moments_pitch;        /* (ignored when moments is NULL) */
+    const float* history;          /* DEVICE width * height floats: rt_reproject's out_history of the colour; NULL = 1 everywhere */
+    void* out;                     /* DEVICE pitched float4 result; out == surface is allowed (below) */
+    uint64_t out_pitch;
+    float* out_variance;           /* DEVICE width * height floats: the last pass's filtered variance; may be NULL */
+    void* scratch;                 /* DEVICE, rt_denoise_variance_scratch_bytes(width, height); contents irrelevant */
+    uint64_t scratch_bytes;
+    /* Filter parameters.  RT_DENOISE_DEFAULT (-1, -1.0f) selects the default (profiles/variance_quality.txt for
+     * sigma_lum and min_history, rt_denoise's for the other three); 0 is an error in all but normal_power_log2. */
+    int32_t iterations;            /* 1..6 (5) */
+    int32_t normal_power_log2;     /* 0..8 (5) */
+    float sigma_plane;             /* > 0, finite (0.03) */
+    float sigma_lum;               /* > 0, finite (4): luminance distance, in standard deviations, that halves a tap */
+    float min_history;             /* >= 1, finite (4): the shortest history whose temporal moments are trusted */
+    int32_t reserved;              /* must be 0 */
+} rt_denoise_variance_params;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_moments_params) == 64 && offsetof(rt_moments_params, surface) == 0 &&
+              offsetof(rt_moments_params, pitch) == 8 && offsetof(rt_moments_params, width) == 16 &&
+              offsetof(rt_moments_params, height) == 20 && offsetof(rt_moments_params, hits) == 24 &&
+              offsetof(rt_moments_params, materials) == 32 && offsetof(rt_moments_params, material_count) == 40 &&
+              offsetof(rt_moments_params, flags) == 44 && offsetof(rt_moments_params, out) == 48 &&
+              offsetof(rt_moments_params, out_pitch) == 56,
+              "rt_moments_params");
+static_assert(sizeof(rt_denoise_variance_params) == 136 && offsetof(rt_denoise_variance_params, surface) == 0 &&
+              offsetof(rt_denoise_variance_params, pitch) == 8 && offsetof(rt_denoise_variance_params, width) == 16 &&
+              offsetof(rt_denoise_variance_params, height) == 20 && offsetof(rt_denoise_variance_params, hits) == 24 &&
+              offsetof(rt_denoise_variance_params, materials) == 32 &&
+              offsetof(rt_denoise_variance_params, material_count) == 40 && offsetof(rt_denoise_variance_params, flags) == 44 &&
+              offsetof(rt_denoise_variance_params, moments) == 48 && offsetof(rt_denoise_variance_params, moments_pitch) == 56 &&
+              offsetof(rt_denoise_variance_params, history) == 64 && offsetof(rt_denoise_variance_params, out) == 72 &&
+              offsetof(rt_denoise_variance_params, out_pitch) == 80 && offsetof(rt_denoise_variance_params, out_variance) == 88 &&
+              offsetof(rt_denoise_variance_params, scratch) == 96 && offsetof(rt_denoise_variance_params, scratch_bytes) == 104 &&
+              offsetof(rt_denoise_variance_params, iterations) == 112 &&
+              offsetof(rt_denoise_variance_params, normal_power_log2) == 116 &&
+              offsetof(rt_denoise_variance_params, sigma_plane) == 120 && offsetof(rt_denoise_variance_params, sigma_lum) == 124 &&
+              offsetof(rt_denoise_variance_params, min_history) == 128 && offsetof(rt_denoise_variance_params, reserved) == 132,
+              "rt_denoise_variance_params");
+#endif
+
+/* The luminance moments of one frame on `stream` (a hipStream_t, NULL = null stream): stream-ordered, no
+ * synchronisation, no allocation, no scratch; one kernel launch.  Every argument is checked on the host before the
+ * launch (NULL pointers, sizes <= 0 or above the limits, pitches, alignment, flags != 0); `out` overlapping
+ * `surface` (out == surface included) or `hits` is refused.  Returns 0 or an error code with rt_last_error(). */
+int rt_moments(const rt_moments_params* params, void* stream);
+/* Bytes of scratch rt_denoise_variance needs for a width x height frame (68 per pixel: the packed guide, two
+ * buffers of colour and variance, one alpha plane; rounded up to 16); 0 for a size <= 0.  Monotone in both arguments. */
+size_t rt_denoise_variance_scratch_bytes(int width, int height);
+/* Filter on `stream` (a hipStream_t, NULL = null stream): stream-ordered, no synchronisation, no allocation;
+ * iterations + 1 kernel launches.  Every argument is checked on the host before the first launch (NULL pointers,
+ * sizes <= 0 or above the limits, pitches < width * 16, alignment -- 16 bytes for surfaces, records and scratch, 4 for
+ * history and out_variance --, scratch too small, flags or reserved != 0, parameters out of range, overlaps).
+ * out == surface is safe: the first kernel consumes the whole surface into scratch, and the last pass, the only one
+ * that writes `out` and `out_variance`, reads scratch and the material table only.  `out` must not overlap scratch,
+ * hits, moments or history; out_variance must not overlap out or scratch.  Returns 0 or an error code with
+ * rt_last_error(). */
+int rt_denoise_variance(const rt_denoise_variance_params* params, void* stream);
+
 /* init_rng for the pixels of one shard: state index s of shard (shard_index, shard_count)
  * of a width x height frame gets curand_init(seed, pixel_id(s), 0).  With shard_count == 1
  * the states are in y*width + x order (reference layout); otherwise they are compact in the

@@ -5,7 +5,7 @@
     python tools/render_image.py --aov PREFIX
     python tools/render_image.py --denoise
     python tools/render_image.py --ao RADIUS
-    python tools/render_image.py --temporal K
+    python tools/render_image.py --temporal K [--variance]
     python tools/render_image.py --panorama W
 
 --aov PREFIX also writes the first-hit images of the same camera (rt.gbuffer: pixel centres, no jitter) as
@@ -15,7 +15,9 @@ same camera's first-hit records, into a surface of its own (the progressive hist
 --ao RADIUS also writes OUT_ao.pfm (linear) / .ppm (8-bit, linear grey): rt.ambient_occlusion of the same camera's
 first-hit records, 8 samples per pixel of length RADIUS (1 = open, 0 = closed, 1 where the camera ray missed).
 --temporal K also writes OUT_temporal.pfm / .ppm: K frames of the config's spp, each rendered with frame_index 0 along a
-small camera dolly that ends at the config's camera, accumulated by rt.TemporalAccumulator (rt_reproject).
+small camera dolly that ends at the config's camera, accumulated by rt.TemporalAccumulator (rt_reproject).  With
+--variance the frames go through rt.VarianceAccumulator instead (the same accumulation, then rt_denoise_variance), which
+adds OUT_filtered.pfm / .ppm and OUT_variance.pfm (linear grey: the filtered variance of the albedo-divided luminance).
 --panorama W also writes OUT_panorama.pfm / .ppm: the W x W/2 equirectangular panorama of the scene from the camera's
 position at the config's spp and bounces (rt.panorama: rt_radiance along rt.panorama_rays).
 """
@@ -50,8 +52,10 @@ def main():
     ap.add_argument("--denoise", action="store_true")
     ap.add_argument("--ao", type=float, default=None, metavar="RADIUS")
     ap.add_argument("--temporal", type=int, default=None, metavar="K")
+    ap.add_argument("--variance", action="store_true", help="with --temporal: also filter (rt_denoise_variance)")
     ap.add_argument("--panorama", type=int, default=None, metavar="W")
     args = ap.parse_args()
+    assert not args.variance or args.temporal is not None, "--variance needs --temporal K"
     rt = G.load_package()
     scene_name, W, H, SPP, BOUNCES, _ = bench.CONFIGS[args.config]
     torch.cuda.set_device(0)
@@ -82,7 +86,7 @@ def main():
         print(f"wrote {args.out}_ao.pfm / .ppm (radius {args.ao:g}, 8 samples)")
     if args.temporal is not None:
         assert args.temporal >= 1
-        acc = rt.TemporalAccumulator(W, H)
+        acc = rt.VarianceAccumulator(W, H) if args.variance else rt.TemporalAccumulator(W, H)
         frame, unused = rt.alloc_surface(W, H), rt.alloc_surface(W, H)
         for k in range(args.temporal):
             b = args.temporal - 1 - k  # steps before the config's camera (position 0, angles 0 / 180)
@@ -90,6 +94,12 @@ def main():
             scene.upload(rng.data_ptr())
             rt.render(scene, frame, unused, W, H, SPP, BOUNCES, 0)
             moving = acc.push(scene, frame)
+        if args.variance:
+            filtered, moving = moving, acc.accumulated
+            rt.write_pfm(args.out + "_filtered.pfm", filtered, W, H)
+            rt.write_ppm(args.out + "_filtered.ppm", rt.tonemap(filtered, W, H))
+            rt.write_pfm(args.out + "_variance.pfm", ao_outputs(acc.variance)[0], W, H)
+            print(f"wrote {args.out}_filtered.pfm / .ppm and {args.out}_variance.pfm (mean variance {float(acc.variance.mean()):.3g})")
         rt.write_pfm(args.out + "_temporal.pfm", moving, W, H)
         rt.write_ppm(args.out + "_temporal.ppm", rt.tonemap(moving, W, H))
         print(f"wrote {args.out}_temporal.pfm / .ppm ({args.temporal} frames x {SPP} spp along a dolly; "
