@@ -331,6 +331,16 @@ def _stream_ptr(stream=None):
     return ctypes.c_void_p(s.cuda_stream)
 
 
+def _scene_ptr(scene):
+    """The GPUScene* of a Scene, or of a GPUScene filled by the caller."""
+    return ctypes.cast(scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene), ctypes.c_void_p)
+
+
+def _is_rays(t):
+    """A float32 CUDA tensor [N, 8] of rt_ray rows."""
+    return t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 8
+
+
 class Scene:
     """RayTracing::Scene mirror (RayTracing/Scene.h:87-129)."""
 
@@ -599,8 +609,7 @@ def render(scene, surface, last, width, height, spp, bounces, frame_index=0, sha
     if stats is not None:
         p.flags |= RT_RENDER_STATS
         p.stats = stats.data_ptr()
-    gpu = scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene)  # Scene, or a GPUScene filled by the caller
-    _check(lib().rt_render(ctypes.byref(p), ctypes.cast(gpu, ctypes.c_void_p), _stream_ptr(stream)), "rt_render")
+    _check(lib().rt_render(ctypes.byref(p), _scene_ptr(scene), _stream_ptr(stream)), "rt_render")
 
 
 def _trace(scene, rays, count, width, height, hits, stream, waves_per_simd):
@@ -613,8 +622,7 @@ def _trace(scene, rays, count, width, height, hits, stream, waves_per_simd):
     p.count, p.width, p.height = count, width, height
     p.hits = hits.data_ptr()
     p.waves_per_simd = int(waves_per_simd)
-    gpu = scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene)
-    _check(lib().rt_trace_rays(ctypes.byref(p), ctypes.cast(gpu, ctypes.c_void_p), _stream_ptr(stream)), "rt_trace_rays")
+    _check(lib().rt_trace_rays(ctypes.byref(p), _scene_ptr(scene), _stream_ptr(stream)), "rt_trace_rays")
     return hits
 
 
@@ -623,7 +631,7 @@ def trace_rays(scene, rays, hits=None, stream=None, waves_per_simd=0):
     tmax, direction, a zero word) on `stream` (default: torch's current stream), as a float32 [N, 12]
     tensor of rt_hit rows (`hits`, or a new one; hit_fields gives typed views).  The scene must have
     been uploaded (Scene.upload; its RNG pointer may be 0 for a scene that is only queried)."""
-    assert rays.dtype == torch.float32 and rays.is_cuda and rays.is_contiguous() and rays.dim() == 2 and rays.shape[1] == 8
+    assert _is_rays(rays)
     return _trace(scene, rays, rays.shape[0], 0, 0, hits, stream, waves_per_simd)
 
 
@@ -665,7 +673,7 @@ def occluded(scene, rays, out=None, stream=None, waves_per_simd=0):
     anything before its tmax, as a uint8 tensor [N] (`out`, or a new one): byte i is `kind != 0` of the record
     trace_rays gives for ray i, for every ray, at a fraction of the cost where the traversal may stop at the first
     occluder.  Stream-ordered on `stream` (default: torch's current stream)."""
-    assert rays.dtype == torch.float32 and rays.is_cuda and rays.is_contiguous() and rays.dim() == 2 and rays.shape[1] == 8
+    assert _is_rays(rays)
     n = rays.shape[0]
     if out is None:
         with _allocating_on(stream):
@@ -676,8 +684,7 @@ def occluded(scene, rays, out=None, stream=None, waves_per_simd=0):
     p = OcclusionParams()
     p.rays, p.count, p.occluded = rays.data_ptr(), n, out.data_ptr()
     p.waves_per_simd = int(waves_per_simd)
-    gpu = scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene)
-    _check(lib().rt_occluded(ctypes.byref(p), ctypes.cast(gpu, ctypes.c_void_p), _stream_ptr(stream)), "rt_occluded")
+    _check(lib().rt_occluded(ctypes.byref(p), _scene_ptr(scene), _stream_ptr(stream)), "rt_occluded")
     return out
 
 
@@ -687,7 +694,7 @@ def radiance(scene, rays, rng, bounces=REFERENCE_BOUNCES, samples=1, out=None, s
     `samples` evaluations of the reference's ray_color along the ray, w = 1.  `rng`: an int32 CUDA tensor of N states
     (ray_rng, alloc_rng), state i read for ray i and written back advanced.  Pass unit directions unless the rays
     reproduce the reference's camera (rt_abi.h).  Stream-ordered on `stream` (default: torch's current stream)."""
-    assert rays.dtype == torch.float32 and rays.is_cuda and rays.is_contiguous() and rays.dim() == 2 and rays.shape[1] == 8
+    assert _is_rays(rays)
     n = rays.shape[0]
     assert rng.dtype == torch.int32 and rng.is_cuda and rng.is_contiguous() and rng.numel() >= n * (RNG_STATE_BYTES // 4)
     if out is None:
@@ -701,8 +708,7 @@ def radiance(scene, rays, rng, bounces=REFERENCE_BOUNCES, samples=1, out=None, s
     p.rays, p.count, p.rng, p.radiance = rays.data_ptr(), n, rng.data_ptr(), out.data_ptr()
     p.bounces, p.samples = int(bounces), int(samples)
     p.waves_per_simd = int(waves_per_simd)
-    gpu = scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene)
-    _check(lib().rt_radiance(ctypes.byref(p), ctypes.cast(gpu, ctypes.c_void_p), _stream_ptr(stream)), "rt_radiance")
+    _check(lib().rt_radiance(ctypes.byref(p), _scene_ptr(scene), _stream_ptr(stream)), "rt_radiance")
     return out
 
 
@@ -817,8 +823,7 @@ def ambient_occlusion(scene, hits, width, height, radius, samples=8, bias=0.001,
         assert scratch.is_cuda and scratch.is_contiguous()
         p.scratch, p.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
     p.waves_per_simd = int(waves_per_simd)
-    gpu = scene.gpu if hasattr(scene, "gpu") else ctypes.pointer(scene)
-    _check(lib().rt_ao(ctypes.byref(p), ctypes.cast(gpu, ctypes.c_void_p), _stream_ptr(stream)), "rt_ao")
+    _check(lib().rt_ao(ctypes.byref(p), _scene_ptr(scene), _stream_ptr(stream)), "rt_ao")
     return out
 
 

@@ -194,6 +194,14 @@ struct Stack {
     }
 };
 constexpr int STACK_PAD_ROWS = 1;  // LDS rows allocated past a Stack's SL entries (at_clamped)
+// What a one-wave kernel declares around `trace` (rt_fast_body.h RT_FAST_KERNEL, rt_batch.h RT_BATCH_KERNEL): SL, the
+// stack's LDS entries, with deeper ones in the private `ovf`; stack_lds, one word per entry (pop) for rtfast::Stack<SL>
+// {stack_lds, ovf}; scratch_lds, coop_tree's compaction (leaf-tree modes) and the deferred leaves.
+#define RT_TRACE_FRAME(STACK, MODE) \
+    constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL; \
+    __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE]; \
+    __shared__ uint32_t scratch_lds[((MODE & rtfast::TREE_BIT) ? 64 : 0) + rtfast::DEFER_WORDS]; \
+    uint32_t ovf[STACK > SL ? STACK - SL : 1];
 
 // Pop stack entries until one passes `tmin < closest` (the reference's pop-time test).  An
 // entry is a node index (lane stride WAVE in LDS); tmin is recomputed from the node with the same

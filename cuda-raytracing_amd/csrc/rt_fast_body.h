@@ -462,11 +462,7 @@ __device__ __forceinline__ void render_fast_body(const RenderArgs& a,
 #define RT_FAST_KERNEL(NAME, ...) \
     template <int STACK, bool STATS, int MODE> \
     __global__ __launch_bounds__(WAVE) __VA_ARGS__ void NAME(RenderArgs a) { \
-        constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL; /* LDS entries; deeper ones in `ovf` (rt_fast.h Stack) */ \
-        __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE]; /* one word per entry (rt_fast.h pop) */ \
-        /* coop_tree's compaction, deferred leaves */ \
-        __shared__ uint32_t scratch_lds[((MODE & rtfast::TREE_BIT) ? 64 : 0) + rtfast::DEFER_WORDS]; \
-        uint32_t ovf[STACK > SL ? STACK - SL : 1]; \
+        RT_TRACE_FRAME(STACK, MODE) \
         render_fast_body<STACK, STATS, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds); \
     }
 RT_FAST_KERNEL(render_fast_kernel, )

@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <vector>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <atomic>
 #include <memory>
@@ -26,6 +27,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 
 #include "rt_abi.h"
 #include "rt_device.h"
@@ -53,6 +55,9 @@ static int check(hipError_t e, const char* what) {
     if (e == hipSuccess) return 0;
     return set_error(std::string(what) + ": " + hipGetErrorString(e), (int)e);
 }
+
+// "who: what" as the last error; 1, the refusing call's return value
+static int refuse(const char* who, const std::string& what) { return set_error(std::string(who) + ": " + what); }
 
 extern "C" const char* rt_last_error(void) { return g_last_error.c_str(); }
 
@@ -729,6 +734,18 @@ static int validate_lone(const int32_t* lone, long long nl, const int32_t* lanes
     return 0;
 }
 
+// The sky of a launch of `who` (rt_render, rt_radiance): the scene's cube map, if it has one, and the sky rotation.
+static int fill_sky(const char* who, const GPUScene* scene, RenderArgs* a) {
+    if (scene->environment_cubemap_tex) {
+        const int n = cube_size(scene->environment_cubemap_tex);
+        if (n <= 0) return refuse(who, "unknown environment cube map handle");
+        a->sky = (const float*)scene->environment_cubemap_tex;
+        a->sky_n = n;
+    }
+    sky_quat(&a->qw, &a->qx, &a->qy, &a->qz);
+    return 0;
+}
+
 extern "C" int rt_render(const rt_render_params* p, const GPUScene* scene, void* stream) {
     if (!p || !scene) return set_error("rt_render: null argument");
     if (p->width <= 0 || p->height <= 0 || p->spp <= 0 || p->bounces < 0)
@@ -753,13 +770,7 @@ extern "C" int rt_render(const rt_render_params* p, const GPUScene* scene, void*
     a.rng = (rt_rng_state*)scene->rng_state;
     a.sphere_count = scene->sphere_count;
     a.cam = scene->camera;
-    if (scene->environment_cubemap_tex) {
-        const int n = cube_size(scene->environment_cubemap_tex);
-        if (n <= 0) return set_error("rt_render: unknown environment cube map handle");
-        a.sky = (const float*)scene->environment_cubemap_tex;
-        a.sky_n = n;
-    }
-    sky_quat(&a.qw, &a.qx, &a.qy, &a.qz);
+    if (fill_sky("rt_render", scene, &a) != 0) return 1;
     a.surface = (char*)p->surface;
     a.last = (const char*)p->surface_last_frame;
     a.out_shard = (float4*)p->out_shard;
@@ -943,105 +954,127 @@ void rt_internal_forget_entry_table(const void* mirror_nodes) {
     g_entry.erase(it);
 }
 
-// The scene half of a query launch, for rt_trace_rays, rt_occluded and rt_ao (`who` names the call in the
-// messages): scenes uploaded by rt_scene_upload only; the mirror arrays a render launch passes to trace; the
-// variant a production frame of this scene runs at RT_TUNE 0 (choose_variant).
-static int query_scene(const char* who, const GPUScene* scene, QueryArgs* out, Variant* variant) {
-    const std::string w(who);
+// The scene half of a ray-batch launch, for rt_trace_rays, rt_occluded, rt_ao and rt_radiance (`who` names the call in
+// the messages): scenes uploaded by rt_scene_upload only; the mirror arrays a render launch passes to trace; the
+// variant a production frame of this scene runs at RT_TUNE 0 (choose_variant).  `a` is a QueryArgs, or the RenderArgs
+// a RadianceArgs begins with: zeroed, then the traversal and shading fields the two name alike.
+template <class Args>
+static int query_scene(const char* who, const GPUScene* scene, Args* a, Variant* variant) {
     MirrorDevice mir;
     if (!rt_internal_lookup_mirror(scene, &mir) || !mir.owned)
-        return set_error(w + ": this GPUScene was not uploaded by rt_scene_upload (a foreign scene has no private "
-                             "mirror to query; foreign scenes are not supported here)");
-    if (!mir.nodes || !mir.tris) return set_error(w + ": the scene's mirror has no triangles to traverse");
+        return refuse(who, "this GPUScene was not uploaded by rt_scene_upload (a foreign scene has no private "
+                           "mirror to query; foreign scenes are not supported here)");
+    if (!mir.nodes || !mir.tris) return refuse(who, "the scene's mirror has no triangles to traverse");
     if (depth_refused(who, mir.depth)) return 1;
-    if (scene->sphere_count > 0 && !scene->gpu_spheres) return set_error(w + ": sphere_count without spheres");
-    QueryArgs q;
-    std::memset(&q, 0, sizeof(q));
-    q.width = q.height = 1;
-    q.cam = scene->camera;
-    q.spheres = scene->gpu_spheres;
-    q.sphere_count = scene->sphere_count;
-    q.scene_fast = mir.fast ? 1 : 0;
-    q.faces = scene->gpu_faces;
-    q.vertices = scene->gpu_vertices;
-    q.nodes = (const GPUBVHNode*)mir.nodes;
-    q.tris = (const FlatTri*)mir.tris;
-    q.pairs = (const float4*)mir.pairs, q.quads = (const float4*)mir.quads, q.units = (const float4*)mir.units;
-    q.tree = (const float4*)mir.tree, q.ltris = (const float4*)mir.ltris, q.spairs = (const float4*)mir.spairs;
-    q.flat = (const float4*)mir.flat;
-    q.face_leaf = (const uint32_t*)mir.face_leaf;
+    if (scene->sphere_count > 0 && !scene->gpu_spheres) return refuse(who, "sphere_count without spheres");
+    std::memset(a, 0, sizeof(*a));
+    if constexpr (std::is_same_v<Args, QueryArgs>) {  // the radiance kernel's RenderArgs has no camera (rt_render.h)
+        a->width = a->height = 1;
+        a->cam = scene->camera;
+    }
+    a->spheres = scene->gpu_spheres;
+    a->sphere_count = scene->sphere_count;
+    a->scene_fast = mir.fast ? 1 : 0;
+    a->faces = scene->gpu_faces;
+    a->vertices = scene->gpu_vertices;
+    a->nodes = (const GPUBVHNode*)mir.nodes;
+    a->tris = (const FlatTri*)mir.tris;
+    a->pairs = (const float4*)mir.pairs, a->quads = (const float4*)mir.quads, a->units = (const float4*)mir.units;
+    a->tree = (const float4*)mir.tree, a->ltris = (const float4*)mir.ltris, a->spairs = (const float4*)mir.spairs;
+    a->flat = (const float4*)mir.flat;
+    a->face_leaf = (const uint32_t*)mir.face_leaf;
     VariantInput in{};  // tune 0, no statistics / lane_cost / refill / screens / entry records
-    in.has_tree = q.tree != nullptr, in.arrays_complete = q.spairs && q.pairs && q.quads && q.units, in.depth = mir.depth;
+    in.has_tree = a->tree != nullptr, in.arrays_complete = a->spairs && a->pairs && a->quads && a->units, in.depth = mir.depth;
     *variant = choose_variant(in);
-    *out = q;
     return 0;
+}
+
+// The checks the four calls share, in the order each call makes them.  Each returns 1 with rt_last_error set.
+static int waves_refused(const char* who, int w) {
+    return (w != 0 && (w < 5 || w > 7)) ? refuse(who, "waves_per_simd must be 0 (default), 5, 6 or 7") : 0;
+}
+static int count_refused(const char* who, int64_t count) {
+    if (count < 0) return refuse(who, "negative count");
+    return count > (int64_t)1 << 31 ? refuse(who, "more than 2^31 rays in one call") : 0;
+}
+static int misaligned(const char* who, const char* names, unsigned align, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= (uintptr_t)p;
+    return (bits & (align - 1)) ? refuse(who, std::string(names) + " must be " + std::to_string(align) + "-byte aligned") : 0;
+}
+// a short buffer would fault the GPU
+static int too_small(const char* who, const char* name, const void* p, size_t need) {
+    return bytes_from(p) < need ? refuse(who, std::string(name) + " too small") : 0;
+}
+
+// The occupancy of a call that asks for none (waves_per_simd 0), measured.  MODE 17 and its lean form run 7 waves per
+// SIMD in every call; the leaf-tree MODE 21 runs 5, or 6 in the any-hit calls.
+//  rt_trace_rays (profiles/query_timing.txt): MODE 17 fits 7 with 2 spilled registers (incoherent rays 1.20 vs 1.35 ms
+//   at 5); MODE 21 spills ~100 there (5.0 vs 3.9 ms).
+//  rt_occluded, rt_ao (profiles/occlusion_timing.txt): MODE 17 at 7 (incoherent rays 0.867 vs 0.874 / 0.929 ms at 6 / 5;
+//   rt_ao 2.92 vs 2.96 / 3.07 ms); MODE 21 at 6, not the query kernel's 5 -- without the deferral it spills 10 registers
+//   there, not 89, and is the fastest on every batch (incoherent rays 4.28 vs 4.57 / 4.86 ms at 5 / 7; rt_ao 25.6 vs
+//   26.9 / 27.5 ms).
+//  rt_radiance (profiles/radiance_timing.txt, 2.07 M six-bounce paths): the lean MODE 17 at 7 (config 2's scene 2.27-2.28
+//   vs 2.28-2.31 / 2.32-2.37 ms at 6 / 5; the panorama 2.23 / 2.22 / 2.31); MODE 21 at 5, as the renderer (config 4's
+//   scene 12.2-12.3 vs 15.8-16.1 / 17.9-18.3 ms at 6 / 7, whose builds spill).  MODE 17 general has no benchmark scene:
+//   it follows the lean form.
+static int batch_waves(int asked, const Variant& v, bool any_hit) {
+    if (asked) return asked;
+    return !(v.mode & rtfast::TREE_BIT) ? 7 : any_hit ? 6 : 5;
 }
 
 // Ray queries (rt_abi.h): argument checks, then the query kernel (rt_query.hip) in the variant a production
 // frame of this scene runs at RT_TUNE 0 (choose_variant).  Stream-ordered: no
 // synchronisation, no allocation.
 extern "C" int rt_trace_rays(const rt_trace_params* p, const GPUScene* scene, void* stream) {
-    if (!p) return set_error("rt_trace_rays: null params");
-    if (!scene) return set_error("rt_trace_rays: null scene");
-    if (!p->hits) return set_error("rt_trace_rays: null hits");
-    if (p->flags != 0) return set_error("rt_trace_rays: flags must be 0");
-    if (p->waves_per_simd != 0 && (p->waves_per_simd < 5 || p->waves_per_simd > 7))
-        return set_error("rt_trace_rays: waves_per_simd must be 0 (default), 5, 6 or 7");
+    const char* const who = "rt_trace_rays";
+    if (!p) return refuse(who, "null params");
+    if (!scene) return refuse(who, "null scene");
+    if (!p->hits) return refuse(who, "null hits");
+    if (p->flags != 0) return refuse(who, "flags must be 0");
+    if (waves_refused(who, p->waves_per_simd)) return 1;
     const bool camera = p->rays == nullptr;
-    if (camera && (p->width <= 0 || p->height <= 0)) return set_error("rt_trace_rays: camera mode needs width, height > 0");
+    if (camera && (p->width <= 0 || p->height <= 0)) return refuse(who, "camera mode needs width, height > 0");
     const int64_t count = camera ? (int64_t)p->width * p->height : p->count;
-    if (count < 0) return set_error("rt_trace_rays: negative count");
-    if (count > (int64_t)1 << 31) return set_error("rt_trace_rays: more than 2^31 rays in one call");
-    if ((((uintptr_t)p->rays) | ((uintptr_t)p->hits)) & 15u) return set_error("rt_trace_rays: rays and hits must be 16-byte aligned");
+    if (count_refused(who, count) || misaligned(who, "rays and hits", 16, {p->rays, p->hits})) return 1;
     if (count == 0) return 0;
 
     QueryArgs q;
     Variant v;
-    if (query_scene("rt_trace_rays", scene, &q, &v) != 0) return 1;
-    // a short buffer would fault the GPU
-    if (!camera && bytes_from(p->rays) < (size_t)count * sizeof(rt_ray)) return set_error("rt_trace_rays: rays too small");
-    if (bytes_from(p->hits) < (size_t)count * sizeof(rt_hit)) return set_error("rt_trace_rays: hits too small");
+    if (query_scene(who, scene, &q, &v) != 0) return 1;
+    if (!camera && too_small(who, "rays", p->rays, (size_t)count * sizeof(rt_ray))) return 1;
+    if (too_small(who, "hits", p->hits, (size_t)count * sizeof(rt_hit))) return 1;
     q.rays = p->rays;
     q.hits = p->hits;
     q.count = count;
     q.width = camera ? p->width : 1, q.height = camera ? p->height : 1;
-    // default occupancy, measured (profiles/query_timing.txt): MODE 17 fits 7 waves per SIMD with 2 spilled
-    // registers (incoherent rays 1.20 vs 1.35 ms at 5); the leaf-tree MODE 21 spills ~100 there (5.0 vs 3.9 ms)
-    const int w = p->waves_per_simd ? p->waves_per_simd : ((v.mode & rtfast::TREE_BIT) ? 5 : 7);
+    const int w = batch_waves(p->waves_per_simd, v, false);
     return check(launch_query(v.stack, v.mode, w, q, (hipStream_t)stream), "query_kernel launch");
 }
 
 // Occlusion queries (rt_abi.h): the checks that need no device first, then the scene's and the buffers', then
 // the any-hit kernel (rt_occlude.hip) in rt_trace_rays' variant.  Stream-ordered: no synchronisation, no allocation.
-// Default occupancy, measured (profiles/occlusion_timing.txt): MODE 17 at 7 waves per SIMD as the query kernel
-// (incoherent rays 0.867 vs 0.874 / 0.929 ms at 6 / 5; rt_ao 2.92 vs 2.96 / 3.07 ms); the leaf-tree MODE 21 at 6, not the
-// query kernel's 5 -- without the deferral it spills 10 registers there, not 89, and is the fastest on every batch
-// (incoherent rays 4.28 vs 4.57 / 4.86 ms at 5 / 7; rt_ao 25.6 vs 26.9 / 27.5 ms).
-static int any_default_waves(const Variant& v) { return (v.mode & rtfast::TREE_BIT) ? 6 : 7; }
-
 extern "C" int rt_occluded(const rt_occlusion_params* p, const GPUScene* scene, void* stream) {
-    if (!p) return set_error("rt_occluded: null params");
-    if (!scene) return set_error("rt_occluded: null scene");
-    if (!p->occluded) return set_error("rt_occluded: null occluded");
-    if (!p->rays) return set_error("rt_occluded: null rays (there is no camera mode)");
-    if (p->flags != 0) return set_error("rt_occluded: flags must be 0");
-    if (p->waves_per_simd != 0 && (p->waves_per_simd < 5 || p->waves_per_simd > 7))
-        return set_error("rt_occluded: waves_per_simd must be 0 (default), 5, 6 or 7");
-    if (p->count < 0) return set_error("rt_occluded: negative count");
-    if (p->count > (int64_t)1 << 31) return set_error("rt_occluded: more than 2^31 rays in one call");
-    if (((uintptr_t)p->rays) & 15u) return set_error("rt_occluded: rays must be 16-byte aligned");
+    const char* const who = "rt_occluded";
+    if (!p) return refuse(who, "null params");
+    if (!scene) return refuse(who, "null scene");
+    if (!p->occluded) return refuse(who, "null occluded");
+    if (!p->rays) return refuse(who, "null rays (there is no camera mode)");
+    if (p->flags != 0) return refuse(who, "flags must be 0");
+    if (waves_refused(who, p->waves_per_simd) || count_refused(who, p->count) || misaligned(who, "rays", 16, {p->rays}))
+        return 1;
     if (p->count == 0) return 0;
 
     OcclusionArgs a;
     Variant v;
-    if (query_scene("rt_occluded", scene, &a.q, &v) != 0) return 1;
-    // a short buffer would fault the GPU
-    if (bytes_from(p->rays) < (size_t)p->count * sizeof(rt_ray)) return set_error("rt_occluded: rays too small");
-    if (bytes_from(p->occluded) < (size_t)p->count) return set_error("rt_occluded: occluded too small");
+    if (query_scene(who, scene, &a.q, &v) != 0) return 1;
+    if (too_small(who, "rays", p->rays, (size_t)p->count * sizeof(rt_ray))) return 1;
+    if (too_small(who, "occluded", p->occluded, (size_t)p->count)) return 1;
     a.q.rays = p->rays;
     a.q.count = p->count;
     a.occluded = p->occluded;
-    const int w = p->waves_per_simd ? p->waves_per_simd : any_default_waves(v);
+    const int w = batch_waves(p->waves_per_simd, v, true);
     return check(launch_occlusion(v.stack, v.mode, w, a, (hipStream_t)stream), "occlusion_kernel launch");
 }
 
@@ -1049,108 +1082,83 @@ extern "C" int rt_occluded(const rt_occlusion_params* p, const GPUScene* scene, 
 extern "C" size_t rt_ao_scratch_bytes(int, int, int) { return 0; }
 
 extern "C" int rt_ao(const rt_ao_params* p, const GPUScene* scene, void* stream) {
-    if (!p) return set_error("rt_ao: null params");
-    if (!scene) return set_error("rt_ao: null scene");
-    if (!p->hits) return set_error("rt_ao: null hits");
-    if (!p->directions) return set_error("rt_ao: null directions");
-    if (!p->ao) return set_error("rt_ao: null ao");
-    if (p->flags != 0) return set_error("rt_ao: flags must be 0");
-    if (p->waves_per_simd != 0 && (p->waves_per_simd < 5 || p->waves_per_simd > 7))
-        return set_error("rt_ao: waves_per_simd must be 0 (default), 5, 6 or 7");
-    if (p->width <= 0 || p->height <= 0) return set_error("rt_ao: width and height must be > 0");
+    const char* const who = "rt_ao";
+    if (!p) return refuse(who, "null params");
+    if (!scene) return refuse(who, "null scene");
+    if (!p->hits) return refuse(who, "null hits");
+    if (!p->directions) return refuse(who, "null directions");
+    if (!p->ao) return refuse(who, "null ao");
+    if (p->flags != 0) return refuse(who, "flags must be 0");
+    if (waves_refused(who, p->waves_per_simd)) return 1;
+    if (p->width <= 0 || p->height <= 0) return refuse(who, "width and height must be > 0");
     const int64_t count = (int64_t)p->width * p->height;
-    if (count > (int64_t)1 << 30) return set_error("rt_ao: more than 2^30 pixels");
-    if (p->direction_count < 1 || p->direction_count > 65536) return set_error("rt_ao: direction_count must be 1..65536");
-    if (p->samples < 1 || p->samples > 64) return set_error("rt_ao: samples must be 1..64");
-    if (!(p->radius > 0.0f)) return set_error("rt_ao: radius must be > 0 and not NaN");
-    if (!(p->bias >= 0.0f) || !(p->bias <= FLT_MAX)) return set_error("rt_ao: bias must be >= 0 and finite");
-    if ((((uintptr_t)p->hits) | ((uintptr_t)p->directions)) & 15u) return set_error("rt_ao: hits and directions must be 16-byte aligned");
-    if (((uintptr_t)p->ao) & 3u) return set_error("rt_ao: ao must be 4-byte aligned");
+    if (count > (int64_t)1 << 30) return refuse(who, "more than 2^30 pixels");
+    if (p->direction_count < 1 || p->direction_count > 65536) return refuse(who, "direction_count must be 1..65536");
+    if (p->samples < 1 || p->samples > 64) return refuse(who, "samples must be 1..64");
+    if (!(p->radius > 0.0f)) return refuse(who, "radius must be > 0 and not NaN");
+    if (!(p->bias >= 0.0f) || !(p->bias <= FLT_MAX)) return refuse(who, "bias must be >= 0 and finite");
+    if (misaligned(who, "hits and directions", 16, {p->hits, p->directions}) || misaligned(who, "ao", 4, {p->ao})) return 1;
     const size_t need = rt_ao_scratch_bytes(p->width, p->height, p->samples);
-    if (need && (!p->scratch || p->scratch_bytes < need)) return set_error("rt_ao: scratch too small (rt_ao_scratch_bytes)");
+    if (need && (!p->scratch || p->scratch_bytes < need)) return refuse(who, "scratch too small (rt_ao_scratch_bytes)");
 
     AoArgs a;
     Variant v;
-    if (query_scene("rt_ao", scene, &a.q, &v) != 0) return 1;
-    if (bytes_from(p->hits) < (size_t)count * sizeof(rt_hit)) return set_error("rt_ao: hits too small");
-    if (bytes_from(p->directions) < (size_t)p->direction_count * 16) return set_error("rt_ao: directions too small");
-    if (bytes_from(p->ao) < (size_t)count * 4) return set_error("rt_ao: ao too small");
+    if (query_scene(who, scene, &a.q, &v) != 0) return 1;
+    if (too_small(who, "hits", p->hits, (size_t)count * sizeof(rt_hit))) return 1;
+    if (too_small(who, "directions", p->directions, (size_t)p->direction_count * 16)) return 1;
+    if (too_small(who, "ao", p->ao, (size_t)count * 4)) return 1;
     a.q.hits = const_cast<rt_hit*>(p->hits);  // read only (rt_render.h AoArgs)
     a.q.count = count;
     a.directions = (const float4*)p->directions;
     a.direction_count = p->direction_count, a.samples = p->samples;
     a.radius = p->radius, a.bias = p->bias;
     a.ao = p->ao;
-    const int w = p->waves_per_simd ? p->waves_per_simd : any_default_waves(v);
+    const int w = batch_waves(p->waves_per_simd, v, true);
     return check(launch_ao(v.stack, v.mode, w, a, (hipStream_t)stream), "ao_kernel launch");
 }
 
 // Radiance along the caller's rays (rt_abi.h): the checks that need no device first, then the scene's and the
 // buffers', then the radiance kernel (rt_radiance.hip) in rt_trace_rays' variant, on a RenderArgs filled as rt_render
 // fills it for a scene of its own.  Stream-ordered: no synchronisation, no allocation.
-// Default occupancy, the fastest measured (profiles/radiance_timing.txt, 2.07 M six-bounce paths): the lean MODE 17 at 7
-// waves per SIMD (config 2's scene 2.27-2.28 vs 2.28-2.31 / 2.32-2.37 ms at 6 / 5; the panorama 2.23 / 2.22 / 2.31); the
-// leaf-tree MODE 21 at 5, as the renderer and rt_trace_rays (config 4's scene 12.2-12.3 vs 15.8-16.1 / 17.9-18.3 ms at
-// 6 / 7, whose builds spill).  MODE 17 general has no benchmark scene: it follows the lean form.
-static int radiance_default_waves(const Variant& v) { return (v.mode & rtfast::TREE_BIT) ? 5 : 7; }
-
 extern "C" int rt_radiance(const rt_radiance_params* p, const GPUScene* scene, void* stream) {
-    if (!p) return set_error("rt_radiance: null params");
-    if (!scene) return set_error("rt_radiance: null scene");
-    if (!p->rays) return set_error("rt_radiance: null rays (there is no camera mode)");
-    if (!p->rng) return set_error("rt_radiance: null rng");
-    if (!p->radiance) return set_error("rt_radiance: null radiance");
-    if (p->flags != 0) return set_error("rt_radiance: flags must be 0");
-    if (p->waves_per_simd != 0 && (p->waves_per_simd < 5 || p->waves_per_simd > 7))
-        return set_error("rt_radiance: waves_per_simd must be 0 (default), 5, 6 or 7");
-    if (p->count < 0) return set_error("rt_radiance: negative count");
-    if (p->count > (int64_t)1 << 31) return set_error("rt_radiance: more than 2^31 rays in one call");
-    if (p->bounces < 0) return set_error("rt_radiance: bounces must be >= 0");
-    if (p->samples < 1 || p->samples > (1 << 24)) return set_error("rt_radiance: samples must be 1..2^24");
-    if ((((uintptr_t)p->rays) | ((uintptr_t)p->radiance)) & 15u)
-        return set_error("rt_radiance: rays and radiance must be 16-byte aligned");
-    if (((uintptr_t)p->rng) & 7u) return set_error("rt_radiance: rng must be 8-byte aligned");
+    const char* const who = "rt_radiance";
+    if (!p) return refuse(who, "null params");
+    if (!scene) return refuse(who, "null scene");
+    if (!p->rays) return refuse(who, "null rays (there is no camera mode)");
+    if (!p->rng) return refuse(who, "null rng");
+    if (!p->radiance) return refuse(who, "null radiance");
+    if (p->flags != 0) return refuse(who, "flags must be 0");
+    if (waves_refused(who, p->waves_per_simd) || count_refused(who, p->count)) return 1;
+    if (p->bounces < 0) return refuse(who, "bounces must be >= 0");
+    if (p->samples < 1 || p->samples > (1 << 24)) return refuse(who, "samples must be 1..2^24");
+    if (misaligned(who, "rays and radiance", 16, {p->rays, p->radiance}) || misaligned(who, "rng", 8, {p->rng})) return 1;
     if (p->count == 0) return 0;
 
-    QueryArgs q;
-    Variant v;
-    if (query_scene("rt_radiance", scene, &q, &v) != 0) return 1;
-    if (!scene->gpu_materials) return set_error("rt_radiance: the scene has no materials");
     RadianceArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.r.spheres = q.spheres, a.r.sphere_count = q.sphere_count;
+    Variant v;
+    if (query_scene(who, scene, &a.r, &v) != 0) return 1;
+    if (!scene->gpu_materials) return refuse(who, "the scene has no materials");
     a.r.materials = scene->gpu_materials;
-    a.r.vertices = q.vertices, a.r.faces = q.faces;
-    a.r.nodes = q.nodes, a.r.tris = q.tris;
-    a.r.pairs = q.pairs, a.r.quads = q.quads, a.r.units = q.units, a.r.tree = q.tree, a.r.ltris = q.ltris;
-    a.r.spairs = q.spairs, a.r.flat = q.flat, a.r.face_leaf = q.face_leaf;
-    a.r.scene_fast = q.scene_fast;
-    if (scene->environment_cubemap_tex) {
-        const int n = cube_size(scene->environment_cubemap_tex);
-        if (n <= 0) return set_error("rt_radiance: unknown environment cube map handle");
-        a.r.sky = (const float*)scene->environment_cubemap_tex;
-        a.r.sky_n = n;
-    }
-    sky_quat(&a.r.qw, &a.r.qx, &a.r.qy, &a.r.qz);
+    if (fill_sky(who, scene, &a.r) != 0) return 1;
     a.r.bounces = p->bounces;
-    // a short buffer would fault the GPU
     const size_t n = (size_t)p->count;
-    if (bytes_from(p->rays) < n * sizeof(rt_ray)) return set_error("rt_radiance: rays too small");
-    if (bytes_from(p->rng) < n * sizeof(rt_rng_state)) return set_error("rt_radiance: rng too small");
-    if (bytes_from(p->radiance) < n * 16) return set_error("rt_radiance: radiance too small");
+    if (too_small(who, "rays", p->rays, n * sizeof(rt_ray)) || too_small(who, "rng", p->rng, n * sizeof(rt_rng_state)) ||
+        too_small(who, "radiance", p->radiance, n * 16))
+        return 1;
     // a lane re-reads its ray per sample and its state at the start: an output row written over either would change them
     auto overlaps = [&](const void* b, size_t bytes) {
         const uintptr_t o = (uintptr_t)p->radiance, x = (uintptr_t)b;
         return o < x + bytes && x < o + n * 16;
     };
-    if (overlaps(p->rays, n * sizeof(rt_ray))) return set_error("rt_radiance: radiance overlaps rays");
-    if (overlaps(p->rng, n * sizeof(rt_rng_state))) return set_error("rt_radiance: radiance overlaps rng");
+    if (overlaps(p->rays, n * sizeof(rt_ray))) return refuse(who, "radiance overlaps rays");
+    if (overlaps(p->rng, n * sizeof(rt_rng_state))) return refuse(who, "radiance overlaps rng");
     a.rays = p->rays;
     a.rng = p->rng;
     a.radiance = (float4*)p->radiance;
     a.count = p->count;
     a.samples = p->samples;
-    const int w = p->waves_per_simd ? p->waves_per_simd : radiance_default_waves(v);
+    const int w = batch_waves(p->waves_per_simd, v, false);
     return check(launch_radiance(v.stack, v.mode, w, a, (hipStream_t)stream), "radiance_kernel launch");
 }
 

@@ -5,21 +5,9 @@
 // lane runs the closest-hit traversal.  The answer of both is one predicate, `kind != 0 && best < tmax` -- the
 // query kernel's own test for writing a hit record -- so byte i is (kind != 0) of rt_trace_rays' record i for
 // every input.  The AO kernel runs the same predicate over `samples` rays per pixel, formed from the pixel's
-// first-hit record by the fixed arithmetic rt_abi.h spells out.  The variants, the LDS stack and the scratch
-// are the query kernel's: MODE 17, 17 | 128 and 21, stacks 30 / 40 / 64, 5 / 6 / 7 waves per SIMD.
-#include <hip/hip_runtime.h>
-
-#include "rt_abi.h"
-#include "rt_device.h"
-#include "rt_math.h"
-#include "rt_common.h"
-#include "leaftree.h"
-#include "rt_fast.h"
-#include "rt_render.h"
-
-#ifndef RT_LDS_SL
-#define RT_LDS_SL 16  // stack entries in LDS, as in rt_fast_body.h
-#endif
+// first-hit record by the fixed arithmetic rt_abi.h spells out.  The kernel frame, the variants and the launch
+// are the ray-batch scaffold's (rt_batch.h), as the query kernel's.
+#include "rt_batch.h"
 
 namespace rtk {
 namespace {
@@ -27,7 +15,7 @@ namespace {
 // Whether ray (ro, rd, tmax) is occluded: what rt_trace_rays reports as kind != 0.  Every lane of the wave
 // calls it (`live` false: no ray on this lane; trace's big-leaf rounds are wave-cooperative).
 template <int STACK, int MODE>
-__device__ __forceinline__ bool occluded(const QueryArgs& q, const rtfast::Stack<(STACK < RT_LDS_SL ? STACK : RT_LDS_SL)>& stk,
+__device__ __forceinline__ bool occluded(const QueryArgs& q, const rtfast::Stack<RT_BATCH_SL(STACK)>& stk,
                                          uint32_t* const scratch, rtm::f3 ro, rtm::f3 rd, float tmax, bool live) {
     // GetRayHit's sphere loop (main_raytracing.cu:87-101) as in query_body: in order and to the end, since a
     // later sphere overrides an earlier one whenever `dist >= best` is false
@@ -61,7 +49,7 @@ __device__ __forceinline__ bool occluded(const QueryArgs& q, const rtfast::Stack
 
 template <int STACK, int MODE>
 __device__ __forceinline__ void occlusion_body(const OcclusionArgs& a,
-                                               const rtfast::Stack<(STACK < RT_LDS_SL ? STACK : RT_LDS_SL)>& stk,
+                                               const rtfast::Stack<RT_BATCH_SL(STACK)>& stk,
                                                uint32_t* const scratch) {
     const long long i = (long long)blockIdx.x * WAVE + (long long)(threadIdx.x & 63u);
     const bool live = i < a.q.count;
@@ -78,7 +66,7 @@ __device__ __forceinline__ void occlusion_body(const OcclusionArgs& a,
 
 // rt_ao (rt_abi.h spells the arithmetic out): pixel i on lane i, its samples one after the other.
 template <int STACK, int MODE>
-__device__ __forceinline__ void ao_body(const AoArgs& a, const rtfast::Stack<(STACK < RT_LDS_SL ? STACK : RT_LDS_SL)>& stk,
+__device__ __forceinline__ void ao_body(const AoArgs& a, const rtfast::Stack<RT_BATCH_SL(STACK)>& stk,
                                         uint32_t* const scratch) {
     const long long i = (long long)blockIdx.x * WAVE + (long long)(threadIdx.x & 63u);
     const bool inside = i < a.q.count;
@@ -109,69 +97,16 @@ __device__ __forceinline__ void ao_body(const AoArgs& a, const rtfast::Stack<(ST
     if (inside) a.ao[i] = valid ? (float)(a.samples - occ) / (float)a.samples : 1.0f;
 }
 
-// The LDS stack and scratch of the query kernel (rt_query.hip RT_QUERY_KERNEL), at 5 / 6 / 7 waves per SIMD.
-#define RT_ANY_KERNEL(NAME, W, ARGS, BODY) \
-    template <int STACK, int MODE> \
-    __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(W))) void NAME(ARGS a) { \
-        constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL; \
-        __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE]; \
-        __shared__ uint32_t scratch_lds[((MODE & rtfast::TREE_BIT) ? 64 : 0) + rtfast::DEFER_WORDS]; \
-        uint32_t ovf[STACK > SL ? STACK - SL : 1]; \
-        BODY<STACK, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds); \
-    }
-RT_ANY_KERNEL(occlusion_kernel_w5, 5, OcclusionArgs, occlusion_body)
-RT_ANY_KERNEL(occlusion_kernel_w6, 6, OcclusionArgs, occlusion_body)
-RT_ANY_KERNEL(occlusion_kernel_w7, 7, OcclusionArgs, occlusion_body)
-RT_ANY_KERNEL(ao_kernel_w5, 5, AoArgs, ao_body)
-RT_ANY_KERNEL(ao_kernel_w6, 6, AoArgs, ao_body)
-RT_ANY_KERNEL(ao_kernel_w7, 7, AoArgs, ao_body)
-#undef RT_ANY_KERNEL
-
-template <int STACK, int MODE>
-hipError_t launch_w(int w, const OcclusionArgs& a, hipStream_t s) {
-    const dim3 grid((unsigned)((a.q.count + WAVE - 1) / WAVE)), block(WAVE);
-    if (w == 7) hipLaunchKernelGGL((occlusion_kernel_w7<STACK, MODE>), grid, block, 0, s, a);
-    else if (w == 6) hipLaunchKernelGGL((occlusion_kernel_w6<STACK, MODE>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((occlusion_kernel_w5<STACK, MODE>), grid, block, 0, s, a);
-    return hipGetLastError();
-}
-template <int STACK, int MODE>
-hipError_t launch_w(int w, const AoArgs& a, hipStream_t s) {
-    const dim3 grid((unsigned)((a.q.count + WAVE - 1) / WAVE)), block(WAVE);
-    if (w == 7) hipLaunchKernelGGL((ao_kernel_w7<STACK, MODE>), grid, block, 0, s, a);
-    else if (w == 6) hipLaunchKernelGGL((ao_kernel_w6<STACK, MODE>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((ao_kernel_w5<STACK, MODE>), grid, block, 0, s, a);
-    return hipGetLastError();
-}
-
-template <int STACK, class A>
-hipError_t dispatch(int mode, int w, const A& a, hipStream_t s) {
-    using namespace rtfast;
-    switch (mode) {
-        case MODE_PROD: return launch_w<STACK, MODE_PROD>(w, a, s);
-        case MODE_PROD | LEAN_BIT: return launch_w<STACK, MODE_PROD | LEAN_BIT>(w, a, s);
-        case MODE_PROD | TREE_BIT: return launch_w<STACK, MODE_PROD | TREE_BIT>(w, a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <class A>
-hipError_t launch_any(int stack, int mode, int waves_per_simd, const A& a, hipStream_t s) {
-    if (a.q.count <= 0 || a.q.count > (1LL << 31)) return hipErrorInvalidValue;
-    switch (stack) {
-        case 30: return dispatch<30>(mode, waves_per_simd, a, s);
-        case 40: return dispatch<40>(mode, waves_per_simd, a, s);
-        default: return dispatch<64>(mode, waves_per_simd, a, s);
-    }
-}
+RT_BATCH_KERNELS(occlusion_kernel, OcclusionArgs, occlusion_body)
+RT_BATCH_KERNELS(ao_kernel, AoArgs, ao_body)
 
 }  // namespace
 
 hipError_t launch_occlusion(int stack, int mode, int waves_per_simd, const OcclusionArgs& a, hipStream_t s) {
-    return launch_any(stack, mode, waves_per_simd, a, s);
+    return launch_batch<occlusion_kernel_set>(stack, mode, waves_per_simd, a.q.count, a, s);
 }
 hipError_t launch_ao(int stack, int mode, int waves_per_simd, const AoArgs& a, hipStream_t s) {
-    return launch_any(stack, mode, waves_per_simd, a, s);
+    return launch_batch<ao_kernel_set>(stack, mode, waves_per_simd, a.q.count, a, s);
 }
 
 }  // namespace rtk

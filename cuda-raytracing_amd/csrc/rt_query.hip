@@ -2,23 +2,9 @@
 // render kernel's traversal.  One ray per lane, wave w owning rays [64w, 64w + 64): the lane reads its ray (or
 // forms the camera ray of its pixel centre), runs GetRayHit's sphere loop and rtfast::trace exactly as
 // render_fast_body does (rt_fast_body.h), and writes one 48-byte hit record with the attributes shade_segment
-// computes -- no RNG, no shading, no sky, no surface.  The variants are the ones a production frame runs at
-// RT_TUNE 0 (rt_variant.h choose_variant): MODE_PROD = 17 or its lean form 17 | 128 for scenes without leaf
-// trees, 21 with them; stacks of 30 / 40 / 64 entries; 5, 6 and 7 waves per SIMD.  rt_kernel.hip picks one
-// (rt_trace_rays).  Compiled with the flags of every other unit (rt_fast_body.h RT_FAST_FAMILY, build.py).
-#include <hip/hip_runtime.h>
-
-#include "rt_abi.h"
-#include "rt_device.h"
-#include "rt_math.h"
-#include "rt_common.h"
-#include "leaftree.h"
-#include "rt_fast.h"
-#include "rt_render.h"
-
-#ifndef RT_LDS_SL
-#define RT_LDS_SL 16  // stack entries in LDS, as in rt_fast_body.h
-#endif
+// computes -- no RNG, no shading, no sky, no surface.  The kernel frame, the variants and the launch are the
+// ray-batch scaffold's (rt_batch.h); rt_kernel.hip picks the variant (rt_trace_rays).
+#include "rt_batch.h"
 
 namespace rtk {
 namespace {
@@ -46,8 +32,7 @@ __device__ __forceinline__ void query_ray(const QueryArgs& q, long long i, rtm::
 }
 
 template <int STACK, int MODE>
-__device__ __forceinline__ void query_body(const QueryArgs& q,
-                                           const rtfast::Stack<(STACK < RT_LDS_SL ? STACK : RT_LDS_SL)>& stk,
+__device__ __forceinline__ void query_body(const QueryArgs& q, const rtfast::Stack<RT_BATCH_SL(STACK)>& stk,
                                            uint32_t* const scratch) {
     const long long i = (long long)blockIdx.x * WAVE + (long long)(threadIdx.x & 63u);
     const bool live = i < q.count;  // lanes past the batch still call trace: its big-leaf rounds are wave-cooperative
@@ -111,50 +96,12 @@ __device__ __forceinline__ void query_body(const QueryArgs& q,
     }
 }
 
-// The LDS stack and scratch of render_fast_kernel (rt_fast_body.h), at 5 / 6 / 7 waves per SIMD.
-#define RT_QUERY_KERNEL(NAME, W) \
-    template <int STACK, int MODE> \
-    __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(W))) void NAME(QueryArgs q) { \
-        constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL; \
-        __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE]; \
-        __shared__ uint32_t scratch_lds[((MODE & rtfast::TREE_BIT) ? 64 : 0) + rtfast::DEFER_WORDS]; \
-        uint32_t ovf[STACK > SL ? STACK - SL : 1]; \
-        query_body<STACK, MODE>(q, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds); \
-    }
-RT_QUERY_KERNEL(query_kernel_w5, 5)
-RT_QUERY_KERNEL(query_kernel_w6, 6)
-RT_QUERY_KERNEL(query_kernel_w7, 7)
-#undef RT_QUERY_KERNEL
-
-template <int STACK, int MODE>
-hipError_t launch_occ(int w, const QueryArgs& q, hipStream_t s) {
-    const dim3 grid((unsigned)((q.count + WAVE - 1) / WAVE)), block(WAVE);
-    if (w == 7) hipLaunchKernelGGL((query_kernel_w7<STACK, MODE>), grid, block, 0, s, q);
-    else if (w == 6) hipLaunchKernelGGL((query_kernel_w6<STACK, MODE>), grid, block, 0, s, q);
-    else hipLaunchKernelGGL((query_kernel_w5<STACK, MODE>), grid, block, 0, s, q);
-    return hipGetLastError();
-}
-
-template <int STACK>
-hipError_t dispatch(int mode, int w, const QueryArgs& q, hipStream_t s) {
-    using namespace rtfast;
-    switch (mode) {
-        case MODE_PROD: return launch_occ<STACK, MODE_PROD>(w, q, s);
-        case MODE_PROD | LEAN_BIT: return launch_occ<STACK, MODE_PROD | LEAN_BIT>(w, q, s);
-        case MODE_PROD | TREE_BIT: return launch_occ<STACK, MODE_PROD | TREE_BIT>(w, q, s);
-    }
-    return hipErrorInvalidValue;
-}
+RT_BATCH_KERNELS(query_kernel, QueryArgs, query_body)
 
 }  // namespace
 
 hipError_t launch_query(int stack, int mode, int waves_per_simd, const QueryArgs& q, hipStream_t s) {
-    if (q.count <= 0 || q.count > (1LL << 31)) return hipErrorInvalidValue;
-    switch (stack) {
-        case 30: return dispatch<30>(mode, waves_per_simd, q, s);
-        case 40: return dispatch<40>(mode, waves_per_simd, q, s);
-        default: return dispatch<64>(mode, waves_per_simd, q, s);
-    }
+    return launch_batch<query_kernel_set>(stack, mode, waves_per_simd, q.count, q, s);
 }
 
 }  // namespace rtk

@@ -5,9 +5,10 @@
 // bounce limit, start the next sample -- so a lane idles only once all its `samples` are done.  Lanes past `count`
 // and lanes that are done keep calling trace with live = false: its big-leaf rounds are wave-cooperative.
 // shade_segment is the renderer's own, on the RenderArgs the argument struct begins with (rt_render.h RadianceArgs),
-// so a ray that is a jittered camera ray gets the renderer's sample bit for bit.  The variants, the LDS stack and the
-// scratch are the query kernel's: MODE 17, 17 | 128 and 21, stacks 30 / 40 / 64, 5 / 6 / 7 waves per SIMD.
+// so a ray that is a jittered camera ray gets the renderer's sample bit for bit.  The kernel frame, the variants and
+// the launch are the ray-batch scaffold's (rt_batch.h), as the query kernel's.
 #include "rt_fast_body.h"
+#include "rt_batch.h"
 
 namespace rtk {
 namespace {
@@ -23,8 +24,7 @@ __device__ __forceinline__ T xarg(const RadianceArgs& a, T RadianceArgs::*m) {
 __device__ __forceinline__ bool is_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
 template <int STACK, int MODE>
-__device__ __forceinline__ void radiance_body(const RadianceArgs& a,
-                                              const rtfast::Stack<(STACK < RT_LDS_SL ? STACK : RT_LDS_SL)>& stk,
+__device__ __forceinline__ void radiance_body(const RadianceArgs& a, const rtfast::Stack<RT_BATCH_SL(STACK)>& stk,
                                               uint32_t* const scratch) {
     constexpr bool COLD = (MODE & rtfast::LEAN_BIT) != 0;  // as render_fast_body: the lean variants read cold fields in place
     auto A = [&](auto member) { return arg<COLD>(a.r, member); };
@@ -119,50 +119,13 @@ __device__ __forceinline__ void radiance_body(const RadianceArgs& a,
     }
 }
 
-// The LDS stack and scratch of the query kernel (rt_query.hip RT_QUERY_KERNEL), at 5 / 6 / 7 waves per SIMD.
-#define RT_RADIANCE_KERNEL(NAME, W) \
-    template <int STACK, int MODE> \
-    __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(W))) void NAME(RadianceArgs a) { \
-        constexpr int SL = STACK < RT_LDS_SL ? STACK : RT_LDS_SL; \
-        __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE]; \
-        __shared__ uint32_t scratch_lds[((MODE & rtfast::TREE_BIT) ? 64 : 0) + rtfast::DEFER_WORDS]; \
-        uint32_t ovf[STACK > SL ? STACK - SL : 1]; \
-        radiance_body<STACK, MODE>(a, rtfast::Stack<SL>{stack_lds, ovf}, scratch_lds); \
-    }
-RT_RADIANCE_KERNEL(radiance_kernel_w5, 5)
-RT_RADIANCE_KERNEL(radiance_kernel_w6, 6)
-RT_RADIANCE_KERNEL(radiance_kernel_w7, 7)
-#undef RT_RADIANCE_KERNEL
-
-template <int STACK, int MODE>
-hipError_t launch_w(int w, const RadianceArgs& a, hipStream_t s) {
-    const dim3 grid((unsigned)((a.count + WAVE - 1) / WAVE)), block(WAVE);
-    if (w == 7) hipLaunchKernelGGL((radiance_kernel_w7<STACK, MODE>), grid, block, 0, s, a);
-    else if (w == 6) hipLaunchKernelGGL((radiance_kernel_w6<STACK, MODE>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((radiance_kernel_w5<STACK, MODE>), grid, block, 0, s, a);
-    return hipGetLastError();
-}
-
-template <int STACK>
-hipError_t dispatch(int mode, int w, const RadianceArgs& a, hipStream_t s) {
-    using namespace rtfast;
-    switch (mode) {
-        case MODE_PROD: return launch_w<STACK, MODE_PROD>(w, a, s);
-        case MODE_PROD | LEAN_BIT: return launch_w<STACK, MODE_PROD | LEAN_BIT>(w, a, s);
-        case MODE_PROD | TREE_BIT: return launch_w<STACK, MODE_PROD | TREE_BIT>(w, a, s);
-    }
-    return hipErrorInvalidValue;
-}
+RT_BATCH_KERNELS(radiance_kernel, RadianceArgs, radiance_body)
 
 }  // namespace
 
 hipError_t launch_radiance(int stack, int mode, int waves_per_simd, const RadianceArgs& a, hipStream_t s) {
-    if (a.count <= 0 || a.count > (1LL << 31) || a.samples < 1 || a.r.bounces < 0) return hipErrorInvalidValue;
-    switch (stack) {
-        case 30: return dispatch<30>(mode, waves_per_simd, a, s);
-        case 40: return dispatch<40>(mode, waves_per_simd, a, s);
-        default: return dispatch<64>(mode, waves_per_simd, a, s);
-    }
+    if (a.samples < 1 || a.r.bounces < 0) return hipErrorInvalidValue;
+    return launch_batch<radiance_kernel_set>(stack, mode, waves_per_simd, a.count, a, s);
 }
 
 }  // namespace rtk
