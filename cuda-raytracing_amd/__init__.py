@@ -159,6 +159,42 @@ class DenoiseVarianceParams(ctypes.Structure):
                 ("sigma_lum", ctypes.c_float), ("min_history", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class SamplePixelsParams(ctypes.Structure):
+    """rt_sample_pixels_params (rt_abi.h)."""
+    _fields_ = [("pixels", ctypes.c_void_p), ("samples", ctypes.c_void_p), ("count", ctypes.c_int64), ("rng", ctypes.c_void_p),
+                ("accum", ctypes.c_void_p), ("accum_pitch", ctypes.c_uint64), ("moments", ctypes.c_void_p),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("bounces", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("waves_per_simd", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class SamplePriorityParams(ctypes.Structure):
+    """rt_sample_priority_params (rt_abi.h)."""
+    _fields_ = [("accum", ctypes.c_void_p), ("accum_pitch", ctypes.c_uint64), ("moments", ctypes.c_void_p),
+                ("priority", ctypes.c_void_p), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
+class SamplePlanParams(ctypes.Structure):
+    """rt_sample_plan_params (rt_abi.h)."""
+    _fields_ = [("priority", ctypes.c_void_p), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("budget", ctypes.c_int64),
+                ("min_samples", ctypes.c_int32), ("max_samples", ctypes.c_int32), ("scale", ctypes.c_float),
+                ("reserved", ctypes.c_int32), ("pixels", ctypes.c_void_p), ("samples", ctypes.c_void_p),
+                ("total", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_uint64)]
+
+
+class SampleResolveParams(ctypes.Structure):
+    """rt_sample_resolve_params (rt_abi.h)."""
+    _fields_ = [("accum", ctypes.c_void_p), ("accum_pitch", ctypes.c_uint64), ("out", ctypes.c_void_p),
+                ("out_pitch", ctypes.c_uint64), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(SamplePixelsParams) == 80 and ctypes.sizeof(SamplePriorityParams) == 40
+assert ctypes.sizeof(SamplePlanParams) == 80 and ctypes.sizeof(SampleResolveParams) == 40
+# AdaptiveSampler.step's scale: priorities are relative variances of the mean, quantised to 0..65535 after the
+# scaling.  The best point of profiles/adaptive_quality.txt's grid (tools/adaptive_quality.py) on both of its scenes:
+# 2^28 saturates every pixel whose relative variance is above 2^-12, so a round is shared almost evenly among the
+# pixels that have not converged, and the few below that get in proportion less.
+SAMPLE_SCALE_DEFAULT = 268435456.0
+
 HIT_MISS, HIT_SPHERE, HIT_TRIANGLE = 0, 1, 2  # rt_hit.kind
 RAY_TMAX = 1e30  # the renderer's own initial closest distance (main_raytracing.cu:85)
 DENOISE_DEFAULT = -1  # RT_DENOISE_DEFAULT: in a filter parameter of rt_denoise, the measured default
@@ -195,6 +231,11 @@ SIGNATURES = {
     "rt_moments": (_I, [ctypes.POINTER(MomentsParams), _P]),
     "rt_denoise_variance_scratch_bytes": (_SZ, [_I, _I]),
     "rt_denoise_variance": (_I, [ctypes.POINTER(DenoiseVarianceParams), _P]),
+    "rt_sample_pixels": (_I, [ctypes.POINTER(SamplePixelsParams), _P, _P]),
+    "rt_sample_priority": (_I, [ctypes.POINTER(SamplePriorityParams), _P]),
+    "rt_sample_plan_scratch_bytes": (_SZ, [_I, _I]),
+    "rt_sample_plan": (_I, [ctypes.POINTER(SamplePlanParams), _P]),
+    "rt_sample_resolve": (_I, [ctypes.POINTER(SampleResolveParams), _P]),
     "rt_foreign_mirror_wait": (_I, [_P]),
     "rt_foreign_last_tracer": (_I, [_P]),
     "rt_experimental_loaded": (_I, []),
@@ -756,6 +797,167 @@ def panorama(scene, width, height, origin=None, samples=REFERENCE_SPP, bounces=R
         surface = alloc_surface(w, h, device=rays.device)
         surface_view(surface, w).copy_(rgba.view(h, w, 4))
     return surface
+
+
+def _is_pitched(t, w, h):
+    """A pitched float4 surface tensor (alloc_surface layout) of at least w x h."""
+    return (t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= h
+            and t.shape[1] >= w * 4 and (t.stride(0) * 4) % 16 == 0)
+
+
+def sample_pixels(scene, width, height, samples, rng, accum, pixels=None, moments=None, bounces=REFERENCE_BOUNCES,
+                  stream=None, waves_per_simd=0):
+    """rt_sample_pixels: samples[i] more of the renderer's samples for pixel pixels[i] (= y * width + x; None: entry i
+    is pixel i) of the uploaded Scene's camera, added to the undivided accumulator `accum` (a pitched surface: sum of
+    rgb, sample count), to `moments` (float32 [H*W, 2], optional) and the pixel's state in `rng` (H*W states in the
+    renderer's layout).  `samples`: int16 / uint16 CUDA tensor (read as uint16), one entry each; `pixels`: int32.
+    Stream-ordered on `stream` (default: torch's current stream)."""
+    w, h = int(width), int(height)
+    assert samples.is_cuda and samples.is_contiguous() and samples.element_size() == 2 and not samples.is_floating_point()
+    n = samples.numel()
+    assert rng.dtype == torch.int32 and rng.is_cuda and rng.is_contiguous() and rng.numel() >= w * h * (RNG_STATE_BYTES // 4)
+    assert _is_pitched(accum, w, h)
+    p = SamplePixelsParams()
+    if pixels is not None:
+        assert pixels.dtype == torch.int32 and pixels.is_cuda and pixels.is_contiguous() and pixels.numel() >= n
+        p.pixels = pixels.data_ptr() if n else None
+    if moments is not None:
+        assert moments.dtype == torch.float32 and moments.is_cuda and moments.is_contiguous() and moments.numel() >= 2 * w * h
+        p.moments = moments.data_ptr()
+    if n == 0:  # rt_sample_pixels returns at once for count 0; an empty tensor has no address to pass
+        return accum
+    p.samples, p.count, p.rng = samples.data_ptr(), n, rng.data_ptr()
+    p.accum, p.accum_pitch = accum.data_ptr(), accum.stride(0) * 4
+    p.width, p.height, p.bounces, p.waves_per_simd = w, h, int(bounces), int(waves_per_simd)
+    _check(lib().rt_sample_pixels(ctypes.byref(p), _scene_ptr(scene), _stream_ptr(stream)), "rt_sample_pixels")
+    return accum
+
+
+def sample_priority(accum, moments, width, height, out=None, stream=None):
+    """rt_sample_priority: float32 [H*W] priorities (`out`, or a new tensor) from an accumulator and its moments: the
+    relative variance of the mean, +inf where fewer than two samples are known."""
+    w, h = int(width), int(height)
+    assert _is_pitched(accum, w, h)
+    assert moments.dtype == torch.float32 and moments.is_cuda and moments.is_contiguous() and moments.numel() >= 2 * w * h
+    if out is None:
+        with _allocating_on(stream):
+            out = torch.empty((w * h,), dtype=torch.float32, device=accum.device)
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.numel() >= w * h
+    p = SamplePriorityParams()
+    p.accum, p.accum_pitch, p.moments, p.priority = accum.data_ptr(), accum.stride(0) * 4, moments.data_ptr(), out.data_ptr()
+    p.width, p.height = w, h
+    _check(lib().rt_sample_priority(ctypes.byref(p), _stream_ptr(stream)), "rt_sample_priority")
+    return out
+
+
+def sample_plan_scratch_bytes(width, height):
+    """rt_sample_plan_scratch_bytes (needs no GPU)."""
+    return int(lib().rt_sample_plan_scratch_bytes(int(width), int(height)))
+
+
+def sample_plan(priority, width, height, budget, min_samples=0, max_samples=64, scale=SAMPLE_SCALE_DEFAULT, pixels=None,
+                samples=None, total=None, scratch=None, stream=None):
+    """rt_sample_plan: the list of the next round from float32 [H*W] priorities and a total `budget` of samples.
+    Returns (pixels int32 [H*W], samples int16 [H*W] holding uint16 counts, total int64 [1]): every pixel once, sorted
+    by count descending, 8x8 sub-tile order inside a count.  Tensors not given are allocated on `stream`."""
+    w, h = int(width), int(height)
+    n = w * h
+    assert priority.dtype == torch.float32 and priority.is_cuda and priority.is_contiguous() and priority.numel() >= n
+    need = sample_plan_scratch_bytes(w, h)
+    with _allocating_on(stream):
+        if pixels is None:
+            pixels = torch.empty((n,), dtype=torch.int32, device=priority.device)
+        if samples is None:
+            samples = torch.empty((n,), dtype=torch.int16, device=priority.device)
+        if total is None:
+            total = torch.empty((1,), dtype=torch.int64, device=priority.device)
+        if scratch is None:
+            scratch = torch.empty((need,), dtype=torch.uint8, device=priority.device)
+    assert pixels.dtype == torch.int32 and pixels.is_cuda and pixels.is_contiguous() and pixels.numel() >= n
+    assert samples.element_size() == 2 and not samples.is_floating_point() and samples.is_cuda and samples.is_contiguous()
+    assert samples.numel() >= n and total.dtype == torch.int64 and total.is_cuda and total.numel() >= 1
+    assert scratch.is_cuda and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= need
+    p = SamplePlanParams()
+    p.priority, p.width, p.height, p.budget = priority.data_ptr(), w, h, int(budget)
+    p.min_samples, p.max_samples, p.scale = int(min_samples), int(max_samples), float(scale)
+    p.pixels, p.samples, p.total = pixels.data_ptr(), samples.data_ptr(), total.data_ptr()
+    p.scratch, p.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
+    _check(lib().rt_sample_plan(ctypes.byref(p), _stream_ptr(stream)), "rt_sample_plan")
+    return pixels, samples, total
+
+
+def sample_resolve(accum, width, height, out=None, stream=None):
+    """rt_sample_resolve: the mean image of an accumulator as a pitched surface (`out`, or a new one): rgb / count where
+    count >= 1, else 0; alpha 1."""
+    w, h = int(width), int(height)
+    assert _is_pitched(accum, w, h)
+    if out is None:
+        with _allocating_on(stream):
+            out = alloc_surface(w, h, device=accum.device)
+    assert _is_pitched(out, w, h)
+    p = SampleResolveParams()
+    p.accum, p.accum_pitch, p.out, p.out_pitch = accum.data_ptr(), accum.stride(0) * 4, out.data_ptr(), out.stride(0) * 4
+    p.width, p.height = w, h
+    _check(lib().rt_sample_resolve(ctypes.byref(p), _stream_ptr(stream)), "rt_sample_resolve")
+    return out
+
+
+class AdaptiveSampler:
+    """Adaptive sampling of an uploaded Scene's camera at width x height (the scene's viewport): it owns the states
+    (rt_init_rng(seed), the renderer's own), the undivided accumulator, the luminance moments, the list of the current
+    round and the planner's scratch.  warmup(spp) gives every pixel spp samples; step(budget_spp) spends
+    budget_spp * width * height samples where the relative variance of the mean is largest.  Every pixel always holds
+    exactly what the renderer's first counts()[y, x] samples of that pixel sum to (rt_abi.h).  Everything runs on
+    `stream` (default: torch's current stream at each call) without synchronisation."""
+
+    def __init__(self, scene, width, height, bounces=REFERENCE_BOUNCES, seed=0xDEADBEEF, device=None, stream=None):
+        self.scene, self.width, self.height, self.bounces, self.seed = scene, int(width), int(height), int(bounces), seed
+        self.stream = stream
+        n = self.width * self.height
+        with _allocating_on(stream):
+            self.rng = alloc_rng(n, device=device)
+            self.accum = alloc_surface(self.width, self.height, device=self.rng.device)
+            self.moments = torch.zeros((n, 2), dtype=torch.float32, device=self.rng.device)
+            self.priority = torch.empty((n,), dtype=torch.float32, device=self.rng.device)
+            self.pixels = torch.empty((n,), dtype=torch.int32, device=self.rng.device)
+            self.samples = torch.empty((n,), dtype=torch.int16, device=self.rng.device)
+            self.total = torch.zeros((1,), dtype=torch.int64, device=self.rng.device)
+            self.scratch = torch.empty((sample_plan_scratch_bytes(self.width, self.height),), dtype=torch.uint8,
+                                       device=self.rng.device)
+        self.reset()
+
+    def reset(self):
+        """Forget every sample: zero accumulator and moments, the states of sample 0."""
+        with _allocating_on(self.stream):
+            self.accum.zero_()
+            self.moments.zero_()
+        init_rng_states(self.rng, self.width, self.height, self.seed, stream=self.stream)
+
+    def warmup(self, spp):
+        """A uniform round: spp samples for every pixel (pixels=None)."""
+        with _allocating_on(self.stream):
+            self.samples.fill_(int(spp))
+        sample_pixels(self.scene, self.width, self.height, self.samples, self.rng, self.accum, moments=self.moments,
+                      bounces=self.bounces, stream=self.stream)
+
+    def step(self, budget_spp, min_samples=0, max_samples=64, scale=SAMPLE_SCALE_DEFAULT):
+        """One adaptive round of at most budget_spp * width * height samples: priority, plan, sample.  `total`
+        (device int64 [1]) then holds the samples the round spent."""
+        budget = int(round(float(budget_spp) * self.width * self.height))
+        sample_priority(self.accum, self.moments, self.width, self.height, out=self.priority, stream=self.stream)
+        sample_plan(self.priority, self.width, self.height, budget, min_samples=min_samples, max_samples=max_samples,
+                    scale=scale, pixels=self.pixels, samples=self.samples, total=self.total, scratch=self.scratch,
+                    stream=self.stream)
+        sample_pixels(self.scene, self.width, self.height, self.samples, self.rng, self.accum, pixels=self.pixels,
+                      moments=self.moments, bounces=self.bounces, stream=self.stream)
+
+    def image(self, out=None):
+        """The mean image as a pitched surface (rt_sample_resolve)."""
+        return sample_resolve(self.accum, self.width, self.height, out=out, stream=self.stream)
+
+    def counts(self):
+        """Samples per pixel so far: float32 [H, W], a view of the accumulator's alpha."""
+        return surface_view(self.accum, self.width)[..., 3]
 
 
 def ao_directions(count=256):
@@ -1456,6 +1658,20 @@ class RayTracer:
         return panorama(self.scene, w, h, origin=origin, samples=self.spp if samples is None else samples,
                         bounces=self.bounces if bounces is None else bounces, seed=self.seed if seed is None else seed,
                         device=self.surface.device, stream=stream)
+
+    def adaptive(self, rounds, budget_spp, warmup=2, bounces=None, seed=None, stream=None, **kw):
+        """An adaptively sampled image of the current camera and size: a new AdaptiveSampler, warmup(`warmup`), then
+        `rounds` steps of budget_spp samples per pixel each (**kw are step()'s min_samples, max_samples, scale).
+        Returns the sampler: image() is the picture, counts() the samples per pixel.  Uploads the scene like
+        process(); the frame index, the surfaces and the tracer's RNG states are left alone."""
+        self.scene.set_viewport(self.width, self.height)
+        self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
+        sampler = AdaptiveSampler(self.scene, self.width, self.height, bounces=self.bounces if bounces is None else bounces,
+                                  seed=self.seed if seed is None else seed, device=self.surface.device, stream=stream)
+        sampler.warmup(warmup)
+        for _ in range(int(rounds)):
+            sampler.step(budget_spp, **kw)
+        return sampler
 
     def reprojected(self, **kw):
         """The current frame accumulated with the frames of earlier calls, whatever cameras they had (a lazily

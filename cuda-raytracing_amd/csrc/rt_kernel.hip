@@ -989,7 +989,7 @@ static int query_scene(const char* who, const GPUScene* scene, Args* a, Variant*
     return 0;
 }
 
-// The checks the four calls share, in the order each call makes them.  Each returns 1 with rt_last_error set.
+// The checks the ray-batch calls share, in the order each call makes them.  Each returns 1 with rt_last_error set.
 static int waves_refused(const char* who, int w) {
     return (w != 0 && (w < 5 || w > 7)) ? refuse(who, "waves_per_simd must be 0 (default), 5, 6 or 7") : 0;
 }
@@ -1019,6 +1019,9 @@ static int too_small(const char* who, const char* name, const void* p, size_t ne
 //   vs 2.28-2.31 / 2.32-2.37 ms at 6 / 5; the panorama 2.23 / 2.22 / 2.31); MODE 21 at 5, as the renderer (config 4's
 //   scene 12.2-12.3 vs 15.8-16.1 / 17.9-18.3 ms at 6 / 7, whose builds spill).  MODE 17 general has no benchmark scene:
 //   it follows the lean form.
+//  rt_sample_pixels (profiles/adaptive_timing.txt, 16.6 M six-bounce samples, 8 a pixel): the lean MODE 17 at 7, a tie with 6
+//   inside the spread (config 2's scene 16.6 vs 16.7 / 17.3 ms at 6 / 5); MODE 21 at 5 (config 4's scene 92 vs 128 / 139 ms at
+//   6 / 7): rt_radiance's choices.
 static int batch_waves(int asked, const Variant& v, bool any_hit) {
     if (asked) return asked;
     return !(v.mode & rtfast::TREE_BIT) ? 7 : any_hit ? 6 : 5;
@@ -1160,6 +1163,69 @@ extern "C" int rt_radiance(const rt_radiance_params* p, const GPUScene* scene, v
     a.samples = p->samples;
     const int w = batch_waves(p->waves_per_simd, v, false);
     return check(launch_radiance(v.stack, v.mode, w, a, (hipStream_t)stream), "radiance_kernel launch");
+}
+
+// More samples for listed pixels (rt_abi.h): the checks that need no device first, in the order the header states,
+// then the scene's and the buffers', then the adaptive kernel (rt_adaptive.hip) in rt_trace_rays' variant, on a
+// RenderArgs filled as rt_radiance's plus the camera, the frame, the states and the accumulator.  Stream-ordered: no
+// synchronisation, no allocation.
+extern "C" int rt_sample_pixels(const rt_sample_pixels_params* p, const GPUScene* scene, void* stream) {
+    const char* const who = "rt_sample_pixels";
+    if (!p) return refuse(who, "null params");
+    if (!scene) return refuse(who, "null scene");
+    if (!p->samples) return refuse(who, "null samples");
+    if (!p->rng) return refuse(who, "null rng");
+    if (!p->accum) return refuse(who, "null accum");
+    if (p->flags != 0) return refuse(who, "flags must be 0");
+    if (p->reserved != 0) return refuse(who, "reserved must be 0");
+    if (waves_refused(who, p->waves_per_simd) || count_refused(who, p->count)) return 1;
+    if (p->width <= 0 || p->height <= 0) return refuse(who, "width and height must be > 0");
+    const int64_t pixel_count = (int64_t)p->width * p->height;
+    if (pixel_count > (int64_t)1 << 30) return refuse(who, "more than 2^30 pixels");
+    if (!p->pixels && p->count != pixel_count) return refuse(who, "null pixels needs count == width * height");
+    if (p->bounces < 0) return refuse(who, "bounces must be >= 0");
+    const size_t row = (size_t)p->width * 16;
+    if (p->accum_pitch < row) return refuse(who, "accum_pitch smaller than width * 16");
+    if (p->accum_pitch & 15u) return refuse(who, "accum_pitch must be a multiple of 16");
+    if (misaligned(who, "accum", 16, {p->accum}) || misaligned(who, "rng and moments", 8, {p->rng, p->moments}) ||
+        misaligned(who, "pixels", 4, {p->pixels}) || misaligned(who, "samples", 2, {p->samples}))
+        return 1;
+    if (p->count == 0) return 0;
+
+    SampleArgs a;
+    std::memset(&a, 0, sizeof(a));
+    Variant v;
+    if (query_scene(who, scene, &a.r, &v) != 0) return 1;
+    if (!scene->gpu_materials) return refuse(who, "the scene has no materials");
+    a.r.materials = scene->gpu_materials;
+    if (fill_sky(who, scene, &a.r) != 0) return 1;
+    const size_t n = (size_t)p->count, px = (size_t)pixel_count;
+    const size_t accum_bytes = (size_t)(p->height - 1) * p->accum_pitch + row;
+    if ((p->pixels && too_small(who, "pixels", p->pixels, n * 4)) || too_small(who, "samples", p->samples, n * 2) ||
+        too_small(who, "rng", p->rng, px * sizeof(rt_rng_state)) || too_small(who, "accum", p->accum, accum_bytes) ||
+        (p->moments && too_small(who, "moments", p->moments, px * 8)))
+        return 1;
+    // a lane re-reads its accumulator per sample: a row written over its state, its moments or the list would change them
+    auto overlaps = [&](const void* b, size_t bytes) {
+        const uintptr_t o = (uintptr_t)p->accum, x = (uintptr_t)b;
+        return b && o < x + bytes && x < o + accum_bytes;
+    };
+    if (overlaps(p->rng, px * sizeof(rt_rng_state))) return refuse(who, "accum overlaps rng");
+    if (overlaps(p->moments, px * 8)) return refuse(who, "accum overlaps moments");
+    if (overlaps(p->pixels, n * 4)) return refuse(who, "accum overlaps pixels");
+    if (overlaps(p->samples, n * 2)) return refuse(who, "accum overlaps samples");
+    a.r.cam = scene->camera;
+    a.r.width = p->width, a.r.height = p->height;
+    a.r.rng = p->rng;
+    a.r.surface = (char*)p->accum;
+    a.r.pitch = p->accum_pitch;
+    a.r.bounces = p->bounces;
+    a.pixels = p->pixels;
+    a.samples = p->samples;
+    a.moments = (float2*)p->moments;
+    a.count = p->count;
+    const int w = batch_waves(p->waves_per_simd, v, false);
+    return check(launch_sample_pixels(v.stack, v.mode, w, a, (hipStream_t)stream), "sample_kernel launch");
 }
 
 // 1 when librt_hip_exp.so's render paths are registered (rt_render.h ExperimentalKernels).

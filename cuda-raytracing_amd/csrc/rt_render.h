@@ -99,6 +99,20 @@ struct RadianceArgs {
 static_assert(offsetof(RadianceArgs, r) == 0, "the kernel-argument segment starts with the RenderArgs");
 hipError_t launch_radiance(int stack, int mode, int waves_per_simd, const RadianceArgs& a, hipStream_t s);
 
+// The adaptive-sampling kernel (rt_adaptive.hip, rt_sample_pixels): render_fast_body's sample state machine over a
+// list of (pixel, samples) entries, the query kernel's variants.  As a RadianceArgs it begins with a RenderArgs: `r`
+// holds what the radiance kernel's does, and the camera, width, height, the RNG array (state y * width + x), the
+// accumulator as `surface` with its `pitch`, and bounces.
+struct SampleArgs {
+    RenderArgs r;
+    const int32_t* pixels;    // null: entry i is pixel i
+    const uint16_t* samples;
+    float2* moments;          // null: none kept
+    long long count;
+};
+static_assert(offsetof(SampleArgs, r) == 0, "the kernel-argument segment starts with the RenderArgs");
+hipError_t launch_sample_pixels(int stack, int mode, int waves_per_simd, const SampleArgs& a, hipStream_t s);
+
 // In librt_hip_exp.so beside its families:
 // The lone-pixel kernel (rt_lone.hip): one wave per slot of `lone_slots`, through the treelets.
 hipError_t launch_lone(const RenderArgs& a, const int32_t* lone_slots, int lone_count, const void* treelets, hipStream_t s);

@@ -811,6 +811,159 @@ size_t rt_denoise_variance_scratch_bytes(int width, int height);
  * rt_last_error(). */
 int rt_denoise_variance(const rt_denoise_variance_params* params, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Adaptive sampling: per-pixel sample budgets.  Four calls, each usable alone:
+ *
+ *   rt_sample_pixels    trace samples[i] more of the renderer's own samples for pixel pixels[i], into an undivided
+ *                       accumulator (sum of colours, sample count), optional luminance moments and the pixel's state
+ *   rt_sample_priority  accumulator + moments -> a per-pixel priority (the relative variance of the mean)
+ *   rt_sample_plan      any float image of priorities + a budget -> the (pixels, samples) list of the next round
+ *   rt_sample_resolve   accumulator -> an image (the mean)
+ *
+ * The invariant: a pixel that has received N samples in total, in however many calls and in whatever list order, holds
+ * exactly the renderer's undivided accumulator after N samples and the renderer's RNG state after N samples.
+ *
+ * The arithmetic is fp32, no contraction, IEEE division, only + - * /, fmaxf and comparisons, and exact integer
+ * arithmetic in the planner, so that tests/adaptive_ref.py restates every call bit for bit.
+ *
+ * rt_sample_pixels.  The camera is scene->camera (as rt_trace_rays' camera mode), the frame is width x height, pixel
+ * index p = y * width + x, state p of `rng` is pixel p's (the renderer's layout, rt_init_rng with one shard).  Per list
+ * entry i with n = samples[i] > 0 and p = pixels[i] (or i when pixels is NULL) inside [0, width * height):
+ *   1. the state of p is loaded;
+ *   2. n times, one of the renderer's samples, exactly as rt_render starts and ends it: draw ru, then rv;
+ *      uv = (((float)x + ru) / (float)width, ((float)y + rv) / (float)height); the unnormalised camera direction
+ *      ((lower_left_corner + horizontal * uv.x) + vertical * uv.y) - origin from the camera origin; then per segment
+ *      the sphere loop, the BVH traversal and ray_color's tail (4 draws per hit, none on a miss), until a miss, Russian
+ *      roulette or `bounces` segments.  With bounces == 0 a sample still consumes its two jitter draws and contributes
+ *      (0, 0, 0), as the renderer's does;
+ *   3. after each sample with colour c, a = accum[p]: a.r = a.r + c.r, a.g = a.g + c.g, a.b = a.b + c.b,
+ *      a.w = a.w + 1.0f; with moments, l = (0.2126f*c.r + 0.7152f*c.g) + 0.0722f*c.b (rt_moments' lum),
+ *      m.x = m.x + l, m.y = m.y + l*l;
+ *   4. the state of p is stored.
+ * An entry with samples[i] == 0 reads and writes nothing for its pixel (its pixels[i] is not read either); an entry
+ * < 0 or >= width * height renders nothing.  Row padding of accum is never written; pixels the list does not name are
+ * never written, in accum, moments or rng.  A pixel named twice in one call gives UNDEFINED values in its accumulator,
+ * moments and state, but no fault; rt_sample_plan never produces such a list.
+ * ------------------------------------------------------------------------------------- */
+typedef struct rt_sample_pixels_params {
+    const int32_t* pixels;   /* DEVICE int32[count], 4-byte aligned; NULL: entry i is pixel i, count == width * height */
+    const uint16_t* samples; /* DEVICE uint16[count], 2-byte aligned */
+    int64_t count;           /* 0 returns at once; at most 2^31 */
+    rt_rng_state* rng;       /* DEVICE, width * height states indexed y * width + x, 8-byte aligned */
+    void* accum;             /* DEVICE pitched float4 (sum r, sum g, sum b, samples), 16-byte aligned */
+    uint64_t accum_pitch;    /* bytes per row: >= width * 16, a multiple of 16 */
+    float* moments;          /* DEVICE float[width * height][2] (sum l, sum l*l), 8-byte aligned; may be NULL */
+    int32_t width, height;   /* > 0, width * height <= 2^30 */
+    int32_t bounces;         /* >= 0 */
+    uint32_t flags;          /* must be 0 */
+    int32_t waves_per_simd;  /* occupancy build of the kernel: 5 / 6 / 7, or 0 = the default
+                                (profiles/adaptive_timing.txt) */
+    int32_t reserved;        /* must be 0 */
+} rt_sample_pixels_params;   /* 80 B */
+
+/* rt_sample_priority, per pixel p: n = accum[p].w, m = moments[p].
+ *   !(n >= 2.0f), or m.x or m.y not finite: priority[p] = +inf (unknown pixels go first);
+ *   else m1 = m.x / n, m2 = m.y / n, var = fmaxf(0, m2 - m1*m1) / n, priority[p] = var / (m1*m1 + 1e-4f). */
+typedef struct rt_sample_priority_params {
+    const void* accum;       /* DEVICE pitched float4, 16-byte aligned */
+    uint64_t accum_pitch;    /* >= width * 16, a multiple of 16 */
+    const float* moments;    /* DEVICE float[width * height][2], 8-byte aligned */
+    float* priority;         /* DEVICE float[width * height], 4-byte aligned; must not overlap accum or moments */
+    int32_t width, height;   /* > 0, width * height <= 2^30 */
+} rt_sample_priority_params; /* 40 B */
+
+/* rt_sample_plan.  P = width * height; the list always has P entries, so no size is read back.  All exact:
+ *   t = priority[p] * scale (fp32);  q_p = !(t < 65535.0f) ? 65535 : (t > 0 ? (uint32_t)t : 0)  (NaN, +inf: 65535);
+ *   Q = sum of q_p (uint64);  B = budget - min_samples * P;  extra_p = Q ? (uint64)q_p * B / Q : 0 (the exact
+ *   quotient, rounded down);  n_p = min(max_samples, min_samples + extra_p).
+ * So the sum of n_p never exceeds budget.  Budget left over by the rounding down and by the cap at max_samples is NOT
+ * redistributed.  Order of the list: the pixels enumerated in 8x8 sub-tile order (sub-tiles row-major over
+ * ceil(width/8) x ceil(height/8), row-major inside a sub-tile, positions outside the image left out), then sorted
+ * stably by n_p descending -- equal counts share waves, neighbours stay together inside a count class, and the
+ * zero-sample entries form the tail.  *total, when given, receives the sum of n_p. */
+typedef struct rt_sample_plan_params {
+    const float* priority;   /* DEVICE float[P], 4-byte aligned (rt_sample_priority's, rt_denoise_variance's out_variance, ...) */
+    int32_t width, height;   /* > 0, P <= 2^30 */
+    int64_t budget;          /* total samples of the coming round; >= min_samples * P */
+    int32_t min_samples;     /* 0 .. max_samples */
+    int32_t max_samples;     /* 1 .. 4095 */
+    float scale;             /* > 0, finite */
+    int32_t reserved;        /* must be 0 */
+    int32_t* pixels;         /* DEVICE int32[P], 4-byte aligned */
+    uint16_t* samples;       /* DEVICE uint16[P], 2-byte aligned */
+    uint64_t* total;         /* DEVICE, 8-byte aligned; may be NULL */
+    void* scratch;           /* DEVICE, 16-byte aligned, rt_sample_plan_scratch_bytes(width, height); contents irrelevant */
+    uint64_t scratch_bytes;
+} rt_sample_plan_params;     /* 80 B */
+
+/* rt_sample_resolve, per pixel: out.rgb = accum.w >= 1.0f ? accum.rgb / accum.w : 0, out.a = 1.  `out` is a surface
+ * rt_denoise, rt_tonemap_srgb8 and rt_write_pfm take as is; it must not overlap accum. */
+typedef struct rt_sample_resolve_params {
+    const void* accum;       /* DEVICE pitched float4, 16-byte aligned */
+    uint64_t accum_pitch;    /* >= width * 16, a multiple of 16 (both pitches) */
+    void* out;               /* DEVICE pitched float4, 16-byte aligned; row padding is never written */
+    uint64_t out_pitch;
+    int32_t width, height;   /* > 0, width * height <= 2^30 */
+} rt_sample_resolve_params;  /* 40 B */
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_sample_pixels_params) == 80 && offsetof(rt_sample_pixels_params, pixels) == 0 &&
+              offsetof(rt_sample_pixels_params, samples) == 8 && offsetof(rt_sample_pixels_params, count) == 16 &&
+              offsetof(rt_sample_pixels_params, rng) == 24 && offsetof(rt_sample_pixels_params, accum) == 32 &&
+              offsetof(rt_sample_pixels_params, accum_pitch) == 40 && offsetof(rt_sample_pixels_params, moments) == 48 &&
+              offsetof(rt_sample_pixels_params, width) == 56 && offsetof(rt_sample_pixels_params, height) == 60 &&
+              offsetof(rt_sample_pixels_params, bounces) == 64 && offsetof(rt_sample_pixels_params, flags) == 68 &&
+              offsetof(rt_sample_pixels_params, waves_per_simd) == 72 && offsetof(rt_sample_pixels_params, reserved) == 76,
+              "rt_sample_pixels_params");
+static_assert(sizeof(rt_sample_priority_params) == 40 && offsetof(rt_sample_priority_params, accum) == 0 &&
+              offsetof(rt_sample_priority_params, accum_pitch) == 8 && offsetof(rt_sample_priority_params, moments) == 16 &&
+              offsetof(rt_sample_priority_params, priority) == 24 && offsetof(rt_sample_priority_params, width) == 32 &&
+              offsetof(rt_sample_priority_params, height) == 36,
+              "rt_sample_priority_params");
+static_assert(sizeof(rt_sample_plan_params) == 80 && offsetof(rt_sample_plan_params, priority) == 0 &&
+              offsetof(rt_sample_plan_params, width) == 8 && offsetof(rt_sample_plan_params, height) == 12 &&
+              offsetof(rt_sample_plan_params, budget) == 16 && offsetof(rt_sample_plan_params, min_samples) == 24 &&
+              offsetof(rt_sample_plan_params, max_samples) == 28 && offsetof(rt_sample_plan_params, scale) == 32 &&
+              offsetof(rt_sample_plan_params, reserved) == 36 && offsetof(rt_sample_plan_params, pixels) == 40 &&
+              offsetof(rt_sample_plan_params, samples) == 48 && offsetof(rt_sample_plan_params, total) == 56 &&
+              offsetof(rt_sample_plan_params, scratch) == 64 && offsetof(rt_sample_plan_params, scratch_bytes) == 72,
+              "rt_sample_plan_params");
+static_assert(sizeof(rt_sample_resolve_params) == 40 && offsetof(rt_sample_resolve_params, accum) == 0 &&
+              offsetof(rt_sample_resolve_params, accum_pitch) == 8 && offsetof(rt_sample_resolve_params, out) == 16 &&
+              offsetof(rt_sample_resolve_params, out_pitch) == 24 && offsetof(rt_sample_resolve_params, width) == 32 &&
+              offsetof(rt_sample_resolve_params, height) == 36,
+              "rt_sample_resolve_params");
+#endif
+
+/* All four run on `stream` (a hipStream_t, NULL = null stream): stream-ordered, no synchronisation, no allocation.
+ * Each returns 0 or an error code with rt_last_error().
+ *
+ * rt_sample_pixels: one kernel launch.  The scene rules are rt_radiance's: uploaded by rt_scene_upload (a GPUScene
+ * filled by another host is refused), materials required, the sky is the scene's cube map under the renderer's
+ * rotation, a BVH deeper than the traversal stack is refused.  Checked in this order, the first fault reported -- no
+ * device needed: NULL params, scene, samples, rng, accum; flags; reserved; waves_per_simd; count < 0 or > 2^31;
+ * width / height <= 0; width * height > 2^30; pixels == NULL with count != width * height; bounces; accum_pitch;
+ * alignment (accum 16, rng and moments 8, pixels 4, samples 2) -- then count == 0 returns 0 -- then the scene, then
+ * the buffer sizes (pixels, samples, rng, accum, moments), then overlaps: accum may not overlap rng, moments, pixels
+ * or samples. */
+int rt_sample_pixels(const rt_sample_pixels_params* params, const GPUScene* scene, void* stream);
+/* One kernel launch.  Checked: NULL pointers, sizes, accum_pitch, alignment, priority overlapping accum or moments. */
+int rt_sample_priority(const rt_sample_priority_params* params, void* stream);
+/* Bytes of scratch rt_sample_plan needs for a width x height frame: 16, + 6 per pixel (the unsorted keys and pixel
+ * indices, each array rounded up to 16 bytes), + an upper bound on the radix sort's own storage, whose exact size only
+ * a device tells: 6 more per pixel (its second buffers of both) + 16 per pixel (digit counters of its blocks) + 64 KiB.
+ * It needs no device; rt_sample_plan checks the sort's real size against it.  0 for a size <= 0; monotone in both
+ * arguments. */
+size_t rt_sample_plan_scratch_bytes(int width, int height);
+/* Three kernels, a memset and a stable radix sort over the bits the largest count needs.  Checked in this order:
+ * NULL params, priority, pixels, samples, scratch; width / height <= 0; more than 2^30 pixels; reserved;
+ * max_samples outside 1..4095; min_samples outside 0..max_samples; scale; budget < min_samples * P; alignment
+ * (scratch 16, total 8, priority and pixels 4, samples 2); scratch_bytes; overlaps among priority, pixels, samples,
+ * total and scratch. */
+int rt_sample_plan(const rt_sample_plan_params* params, void* stream);
+/* One kernel launch.  Checked: NULL pointers, sizes, pitches, alignment, out overlapping accum (out == accum too). */
+int rt_sample_resolve(const rt_sample_resolve_params* params, void* stream);
+
 /* init_rng for the pixels of one shard: state index s of shard (shard_index, shard_count)
  * of a width x height frame gets curand_init(seed, pixel_id(s), 0).  With shard_count == 1
  * the states are in y*width + x order (reference layout); otherwise they are compact in the

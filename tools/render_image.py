@@ -7,6 +7,7 @@
     python tools/render_image.py --ao RADIUS
     python tools/render_image.py --temporal K [--variance]
     python tools/render_image.py --panorama W
+    python tools/render_image.py --adaptive ROUNDS
 
 --aov PREFIX also writes the first-hit images of the same camera (rt.gbuffer: pixel centres, no jitter) as
 PREFIX_normal.pfm (normal * 0.5 + 0.5), PREFIX_depth.pfm (hit distance, inf on a miss) and PREFIX_albedo.pfm.
@@ -20,6 +21,9 @@ small camera dolly that ends at the config's camera, accumulated by rt.TemporalA
 adds OUT_filtered.pfm / .ppm and OUT_variance.pfm (linear grey: the filtered variance of the albedo-divided luminance).
 --panorama W also writes OUT_panorama.pfm / .ppm: the W x W/2 equirectangular panorama of the scene from the camera's
 position at the config's spp and bounces (rt.panorama: rt_radiance along rt.panorama_rays).
+--adaptive ROUNDS also writes OUT_adaptive.pfm / .ppm and OUT_samples.pfm: rt.AdaptiveSampler at the config's camera --
+a warm-up of 2 samples a pixel, then ROUNDS rounds that each spend at most the config's spp per pixel where the relative
+variance of the mean is largest -- and its samples per pixel as a linear grey image.
 """
 import argparse
 import os
@@ -54,6 +58,7 @@ def main():
     ap.add_argument("--temporal", type=int, default=None, metavar="K")
     ap.add_argument("--variance", action="store_true", help="with --temporal: also filter (rt_denoise_variance)")
     ap.add_argument("--panorama", type=int, default=None, metavar="W")
+    ap.add_argument("--adaptive", type=int, default=None, metavar="ROUNDS")
     args = ap.parse_args()
     assert not args.variance or args.temporal is not None, "--variance needs --temporal K"
     rt = G.load_package()
@@ -111,6 +116,18 @@ def main():
         rt.write_pfm(args.out + "_panorama.pfm", pano, pw, ph)
         rt.write_ppm(args.out + "_panorama.ppm", rt.tonemap(pano, pw, ph))
         print(f"wrote {args.out}_panorama.pfm / .ppm ({pw}x{ph} equirectangular from the camera's position, {SPP} spp)")
+    if args.adaptive is not None:
+        assert args.adaptive >= 0
+        sampler = rt.AdaptiveSampler(scene, W, H, bounces=BOUNCES, seed=bench.SEED)
+        sampler.warmup(2)
+        for _ in range(args.adaptive):
+            sampler.step(SPP)
+        image, counts = sampler.image(), sampler.counts()
+        rt.write_pfm(args.out + "_adaptive.pfm", image, W, H)
+        rt.write_ppm(args.out + "_adaptive.ppm", rt.tonemap(image, W, H))
+        rt.write_pfm(args.out + "_samples.pfm", ao_outputs(counts.contiguous())[0], W, H)
+        print(f"wrote {args.out}_adaptive.pfm / .ppm and {args.out}_samples.pfm ({args.adaptive} rounds of at most {SPP} spp after 2: "
+              f"{float(counts.mean()):.2f} samples a pixel, {int(counts.min())} to {int(counts.max())})")
     if args.aov:
         g = rt.gbuffer(scene, W, H)
         images = {"normal": g["normal"] * 0.5 + 0.5,
