@@ -1039,13 +1039,10 @@ def _allocating_on(stream):
     return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
 
 
-def _denoise(surface, hits, materials_ptr, material_count, width, height, out, scratch, iterations, normal_power_log2,
-             sigma_plane, sigma_color, stream):
+def _denoise(surface, hits, materials, width, height, out, scratch, iterations, normal_power_log2, sigma_plane, sigma_color,
+             stream):
     w, h = int(width), int(height)
-    assert surface.dtype == torch.float32 and surface.is_cuda and surface.dim() == 2 and surface.stride(1) == 1
-    assert surface.shape[0] >= h and surface.shape[1] >= 4 * w
-    assert hits.dtype == torch.float32 and hits.is_cuda and hits.is_contiguous() and hits.dim() == 2
-    assert hits.shape[1] == 12 and hits.shape[0] >= w * h
+    assert _is_surface(surface, w, h) and _is_hits(hits, w, h)
     need = denoise_scratch_bytes(w, h)
     # what is allocated here is allocated on the stream the kernels run on: the zero fill of `out` is ordered before
     # them, and the caching allocator does not hand the scratch to another stream's work while they still run
@@ -1054,13 +1051,13 @@ def _denoise(surface, hits, materials_ptr, material_count, width, height, out, s
             out = alloc_surface(w, h, device=surface.device)
         if scratch is None:
             scratch = torch.empty((need // 4,), dtype=torch.float32, device=surface.device)
-    assert out.dtype == torch.float32 and out.is_cuda and out.dim() == 2 and out.stride(1) == 1
-    assert out.shape[0] >= h and out.shape[1] >= 4 * w
+    assert _is_surface(out, w, h)
     assert scratch.is_cuda and scratch.is_contiguous()
     p = DenoiseParams()
     p.surface, p.pitch = surface.data_ptr(), surface.stride(0) * 4
     p.width, p.height = w, h
-    p.hits, p.materials, p.material_count = hits.data_ptr(), materials_ptr, int(material_count)
+    p.hits = hits.data_ptr()
+    p.materials, p.material_count = _materials_of(materials)
     p.out, p.out_pitch = out.data_ptr(), out.stride(0) * 4
     p.scratch, p.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
     p.iterations, p.normal_power_log2 = int(iterations), int(normal_power_log2)
@@ -1078,10 +1075,9 @@ def denoise_raw(surface, hits, materials, width, height, out=None, scratch=None,
     irrelevant (allocated when None).  A filter parameter left at DENOISE_DEFAULT takes the library's default
     (DENOISE_DEFAULTS).  Stream-ordered on `stream` (default: torch's current stream); tensors allocated here are
     allocated on that stream, tensors passed in must be safe to use on it."""
-    assert materials.dtype == torch.float32 and materials.is_cuda and materials.is_contiguous()
-    assert materials.dim() == 2 and materials.shape[1] == 16
-    return _denoise(surface, hits, materials.data_ptr() if materials.shape[0] else None, materials.shape[0], width, height,
-                    out, scratch, iterations, normal_power_log2, sigma_plane, sigma_color, stream)
+    assert isinstance(materials, torch.Tensor)
+    return _denoise(surface, hits, materials, width, height, out, scratch, iterations, normal_power_log2, sigma_plane,
+                    sigma_color, stream)
 
 
 def denoise(scene, surface, width, height, hits=None, out=None, scratch=None, iterations=DENOISE_DEFAULT,
@@ -1093,9 +1089,8 @@ def denoise(scene, surface, width, height, hits=None, out=None, scratch=None, it
     if hits is None:
         with _allocating_on(stream):
             hits = trace_camera(scene, width, height, stream=stream)
-    gpu = scene.gpu.contents if hasattr(scene, "gpu") else scene
-    return _denoise(surface, hits, gpu.gpu_materials, gpu.material_count, width, height, out, scratch, iterations,
-                    normal_power_log2, sigma_plane, sigma_color, stream)
+    return _denoise(surface, hits, scene, width, height, out, scratch, iterations, normal_power_log2, sigma_plane,
+                    sigma_color, stream)
 
 
 def _as_camera(camera):

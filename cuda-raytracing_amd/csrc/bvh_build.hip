@@ -39,10 +39,9 @@
 #include <string>
 #include <vector>
 
+#include "mirror.h"  // rt_internal_set_error
 #include "rt_abi.h"
 #include "rt_math.h"
-
-void rt_internal_set_error(const char* msg);
 
 namespace {
 

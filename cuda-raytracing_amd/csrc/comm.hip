@@ -19,9 +19,8 @@
 #include <new>
 #include <string>
 
+#include "mirror.h"  // rt_internal_set_error
 #include "rt_abi.h"
-
-void rt_internal_set_error(const char* msg);
 
 struct rt_comm {
     ncclComm_t nccl;

@@ -12,7 +12,7 @@
 
 #include <cstdint>
 
-#include "mirror.h"  // rt_internal_set_error
+#include "image_entry.h"
 #include "rt_abi.h"
 
 namespace {
@@ -46,10 +46,8 @@ __global__ __launch_bounds__(256) void tonemap_kernel(const char* surface, uint6
 
 extern "C" int rt_tonemap_srgb8(const void* surface, uint64_t pitch, int width, int height, uint8_t* out_rgb,
                                 void* stream) {
-    if (!surface || !out_rgb || width <= 0 || height <= 0 || pitch < (uint64_t)width * 16) {
-        rt_internal_set_error("rt_tonemap_srgb8: bad arguments");
-        return 1;
-    }
+    if (!surface || !out_rgb || width <= 0 || height <= 0 || pitch < (uint64_t)width * 16)
+        return rt_entry::refuse("rt_tonemap_srgb8", "bad arguments");
     hipLaunchKernelGGL(tonemap_kernel, dim3((width + 255) / 256, height), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const char*>(surface), pitch, width, height, out_rgb);
     const hipError_t e = hipGetLastError();

@@ -15,14 +15,16 @@
 // loading a tap's normal and position only after its cheap tests passed is 24 % slower, a 32 x 8-pixel block 1 %.
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
 #include <cstdint>
-#include <cstdio>
 
-#include "mirror.h"  // rt_internal_set_error
+#include "atrous.h"  // finite1, finite3
+#include "image_entry.h"
 #include "rt_abi.h"
 
 namespace {
+
+using atrous::finite3;
+using namespace rt_entry;
 
 // the defaults RT_REPROJECT_DEFAULT selects, chosen from profiles/reproject_quality.txt: the error
 // is flat beyond a history of 32 frames and does not depend on sigma_plane there; normal_min 0.99 loses history
@@ -39,9 +41,6 @@ __host__ __device__ __forceinline__ V3 cross3(const V3& a, const V3& b) {
     return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
 __host__ __device__ __forceinline__ V3 sub3(const V3& a, const V3& b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-
-__device__ __forceinline__ bool finite1(float v) { return fabsf(v) <= FLT_MAX; }
-__device__ __forceinline__ bool finite3(const float4& c) { return finite1(c.x) && finite1(c.y) && finite1(c.z); }
 
 struct ReprojectArgs {
     const char* surface;
@@ -136,58 +135,40 @@ __global__ __launch_bounds__(256) void reproject_kernel(const ReprojectArgs a) {
     a.out_history[p] = oh;
 }
 
-int fail(const char* msg) {
-    rt_internal_set_error(msg);
-    return 1;
-}
-
 V3 ld3(const float v[3]) { return V3{v[0], v[1], v[2]}; }
-
-// [a, a + an) and [b, b + bn) share a byte
-bool overlap(const void* a, uint64_t an, const void* b, uint64_t bn) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bn && y < x + an;
-}
 
 }  // namespace
 
 extern "C" int rt_reproject(const rt_reproject_params* p, void* stream) {
-    if (!p) return fail("rt_reproject: null params");
-    if (!p->surface) return fail("rt_reproject: null surface");
-    if (!p->hits) return fail("rt_reproject: null hits");
-    if (!p->out) return fail("rt_reproject: null out");
-    if (!p->out_history) return fail("rt_reproject: null out_history");
+    const char* const who = "rt_reproject";
+    if (!p) return refuse(who, "null params");
+    if (!p->surface) return refuse(who, "null surface");
+    if (!p->hits) return refuse(who, "null hits");
+    if (!p->out) return refuse(who, "null out");
+    if (!p->out_history) return refuse(who, "null out_history");
     const int prevs = (p->prev_surface != nullptr) + (p->prev_hits != nullptr) + (p->prev_history != nullptr);
-    if (prevs != 0 && prevs != 3)
-        return fail("rt_reproject: prev_surface, prev_hits and prev_history must be all NULL or all non-NULL");
+    if (prevs != 0 && prevs != 3) return refuse(who, "prev_surface, prev_hits and prev_history must be all NULL or all non-NULL");
     const bool has_prev = prevs == 3;
-    if (p->width <= 0 || p->height <= 0) return fail("rt_reproject: width and height must be > 0");
-    // the launch grid: a row of blocks per 4 pixel rows in grid.y, at most 65,535
-    if (p->height > RT_REPROJECT_MAX_HEIGHT) return fail("rt_reproject: height above RT_REPROJECT_MAX_HEIGHT");
-    if ((int64_t)p->width * p->height > RT_REPROJECT_MAX_PIXELS) return fail("rt_reproject: more than RT_REPROJECT_MAX_PIXELS pixels");
-    const uint64_t row = (uint64_t)p->width * 16;
-    if (p->pitch < row) return fail("rt_reproject: pitch smaller than width * 16");
-    if (p->out_pitch < row) return fail("rt_reproject: out_pitch smaller than width * 16");
-    if (has_prev && p->prev_pitch < row) return fail("rt_reproject: prev_pitch smaller than width * 16");
-    if ((p->pitch | p->out_pitch | (has_prev ? p->prev_pitch : 0)) & 15u) return fail("rt_reproject: pitches must be multiples of 16");
-    if (((uintptr_t)p->surface | (uintptr_t)p->hits | (uintptr_t)p->out | (uintptr_t)p->prev_surface | (uintptr_t)p->prev_hits) & 15u)
-        return fail("rt_reproject: surface, hits, prev_surface, prev_hits and out must be 16-byte aligned");
-    if (((uintptr_t)p->out_history | (uintptr_t)p->prev_history) & 3u)
-        return fail("rt_reproject: prev_history and out_history must be 4-byte aligned");
-    if (p->flags != 0) return fail("rt_reproject: flags must be 0");
-    const int max_history = p->max_history == RT_REPROJECT_DEFAULT ? DEFAULT_MAX_HISTORY : p->max_history;
-    const float sigma_plane = p->sigma_plane == (float)RT_REPROJECT_DEFAULT ? DEFAULT_SIGMA_PLANE : p->sigma_plane;
-    const float normal_min = p->normal_min == (float)RT_REPROJECT_DEFAULT ? DEFAULT_NORMAL_MIN : p->normal_min;
-    if (max_history < 1 || max_history > 65535) return fail("rt_reproject: max_history must be 1..65535 (or RT_REPROJECT_DEFAULT)");
-    if (!(sigma_plane > 0.0f) || !(sigma_plane <= FLT_MAX)) return fail("rt_reproject: sigma_plane must be > 0 and finite (or RT_REPROJECT_DEFAULT)");
-    if (!(normal_min >= -1.0f) || !(normal_min <= 1.0f)) return fail("rt_reproject: normal_min must be in [-1, 1] (or RT_REPROJECT_DEFAULT)");
-    const uint64_t n = (uint64_t)p->width * (uint64_t)p->height;
+    if (size_refused(who, p->width, p->height) || caps_refused(who, p->width, p->height, "REPROJECT")) return 1;
+    if (pitch_refused(who, "pitch", p->pitch, p->width) || pitch_refused(who, "out_pitch", p->out_pitch, p->width)) return 1;
+    if (has_prev && pitch_refused(who, "prev_pitch", p->prev_pitch, p->width)) return 1;
+    if (pitches_refused(who, {p->pitch, p->out_pitch, has_prev ? p->prev_pitch : 0})) return 1;
+    if (misaligned(who, "surface, hits, prev_surface, prev_hits and out", 16, {p->surface, p->hits, p->out, p->prev_surface, p->prev_hits}))
+        return 1;
+    if (misaligned(who, "prev_history and out_history", 4, {p->out_history, p->prev_history})) return 1;
+    if (p->flags != 0) return refuse(who, "flags must be 0");
+    const int max_history = or_default(p->max_history, RT_REPROJECT_DEFAULT, DEFAULT_MAX_HISTORY);
+    const float sigma_plane = or_default(p->sigma_plane, RT_REPROJECT_DEFAULT, DEFAULT_SIGMA_PLANE);
+    const float normal_min = or_default(p->normal_min, RT_REPROJECT_DEFAULT, DEFAULT_NORMAL_MIN);
+    if (max_history < 1 || max_history > 65535) return refuse(who, "max_history must be 1..65535 (or RT_REPROJECT_DEFAULT)");
+    if (!finite_above(sigma_plane, 0.0f)) return refuse(who, "sigma_plane must be > 0 and finite (or RT_REPROJECT_DEFAULT)");
+    if (!(normal_min >= -1.0f) || !(normal_min <= 1.0f)) return refuse(who, "normal_min must be in [-1, 1] (or RT_REPROJECT_DEFAULT)");
+    const uint64_t n = (uint64_t)p->width * (uint64_t)p->height, row = (uint64_t)p->width * 16;
     if (has_prev) {
         // other lanes gather from the previous image and history while this one writes
-        const uint64_t out_bytes = (uint64_t)(p->height - 1) * p->out_pitch + row;
-        const uint64_t prev_bytes = (uint64_t)(p->height - 1) * p->prev_pitch + row;
-        if (overlap(p->out, out_bytes, p->prev_surface, prev_bytes)) return fail("rt_reproject: out must not overlap prev_surface");
-        if (overlap(p->out_history, n * 4, p->prev_history, n * 4)) return fail("rt_reproject: out_history must not overlap prev_history");
+        if (overlap(p->out, surface_bytes(p->height, p->out_pitch, row), p->prev_surface, surface_bytes(p->height, p->prev_pitch, row)))
+            return refuse(who, "out must not overlap prev_surface");
+        if (overlap(p->out_history, n * 4, p->prev_history, n * 4)) return refuse(who, "out_history must not overlap prev_history");
     }
 
     ReprojectArgs a;
@@ -208,12 +189,6 @@ extern "C" int rt_reproject(const rt_reproject_params* p, void* stream) {
     a.wn = dot3(w, a.pn);
     a.width = p->width, a.height = p->height;
     a.max_history = (float)max_history, a.sigma_plane = sigma_plane, a.normal_min = normal_min;
-    hipLaunchKernelGGL(reproject_kernel, dim3((p->width + 63) / 64, (p->height + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "rt_reproject: launch failed: %s", hipGetErrorString(e));
-        return fail(msg);
-    }
-    return 0;
+    hipLaunchKernelGGL(reproject_kernel, image_grid(p->width, p->height), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_refused(who);
 }

@@ -39,6 +39,7 @@
 
 #include "mirror.h"
 #include "entry_frontier.h"
+#include "image_entry.h"
 
 static_assert(MIRROR_BIG_LEAF == (uint32_t)rtfast::BIG, "pair records exist for exactly the big leaves");
 
@@ -56,8 +57,8 @@ static int check(hipError_t e, const char* what) {
     return set_error(std::string(what) + ": " + hipGetErrorString(e), (int)e);
 }
 
-// "who: what" as the last error; 1, the refusing call's return value
-static int refuse(const char* who, const std::string& what) { return set_error(std::string(who) + ": " + what); }
+using rt_entry::misaligned;  // image_entry.h: what a refusing call says, through rt_internal_set_error below
+using rt_entry::refuse;
 
 extern "C" const char* rt_last_error(void) { return g_last_error.c_str(); }
 
@@ -996,11 +997,6 @@ static int waves_refused(const char* who, int w) {
 static int count_refused(const char* who, int64_t count) {
     if (count < 0) return refuse(who, "negative count");
     return count > (int64_t)1 << 31 ? refuse(who, "more than 2^31 rays in one call") : 0;
-}
-static int misaligned(const char* who, const char* names, unsigned align, std::initializer_list<const void*> ptrs) {
-    uintptr_t bits = 0;
-    for (const void* p : ptrs) bits |= (uintptr_t)p;
-    return (bits & (align - 1)) ? refuse(who, std::string(names) + " must be " + std::to_string(align) + "-byte aligned") : 0;
 }
 // a short buffer would fault the GPU
 static int too_small(const char* who, const char* name, const void* p, size_t need) {

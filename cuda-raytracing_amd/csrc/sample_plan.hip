@@ -14,14 +14,14 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <cfloat>
 #include <cstdint>
-#include <cstdio>
 
+#include "image_entry.h"
 #include "rt_abi.h"
-#include "mirror.h"  // rt_internal_set_error
 
 namespace {
+
+using namespace rt_entry;
 
 constexpr int64_t kMaxPixels = (int64_t)1 << 30;
 
@@ -105,24 +105,6 @@ __global__ __launch_bounds__(256) void keys_to_counts(uint16_t* samples, uint32_
     if (i < pixels) samples[i] = (uint16_t)(max_samples - samples[i]);
 }
 
-int fail(const char* msg) {
-    rt_internal_set_error(msg);
-    return 1;
-}
-
-int hip_error(const char* call, const char* what, hipError_t e) {
-    if (e == hipSuccess) return 0;
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: %s: %s", call, what, hipGetErrorString(e));
-    return fail(msg);
-}
-
-// [a, a + an) and [b, b + bn) share a byte
-bool overlap(const void* a, uint64_t an, const void* b, uint64_t bn) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + bn && y < x + an;
-}
-
 size_t round16(size_t n) { return (n + 15u) & ~(size_t)15u; }
 
 // scratch: [0, 16) the cells, then the unsorted keys, the unsorted values, the sort's storage
@@ -139,57 +121,51 @@ PlanLayout plan_layout(size_t n) {
     return l;
 }
 
-dim3 image_grid(int width, int height) { return dim3((unsigned)((width + 63) / 64), (unsigned)((height + 3) / 4)); }
-
-// the checks the pitched-accumulator calls share; `row` = width * 16
-int image_refused(const char* who, int width, int height, const void* accum, uint64_t pitch) {
-    char msg[160];
-    const char* what = nullptr;
-    if (width <= 0 || height <= 0) what = "width and height must be > 0";
-    else if ((int64_t)width * height > kMaxPixels) what = "more than 2^30 pixels";
-    else if (pitch < (uint64_t)width * 16) what = "accum_pitch smaller than width * 16";
-    else if (pitch & 15u) what = "accum_pitch must be a multiple of 16";
-    else if ((uintptr_t)accum & 15u) what = "accum must be 16-byte aligned";
-    if (!what) return 0;
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return fail(msg);
+// the checks the pitched-accumulator calls share
+int accum_refused(const char* who, int width, int height, const void* accum, uint64_t pitch) {
+    if (size_refused(who, width, height)) return 1;
+    if ((int64_t)width * height > kMaxPixels) return refuse(who, "more than 2^30 pixels");
+    if (pitch_refused(who, "accum_pitch", pitch, width)) return 1;
+    if (pitch & 15u) return refuse(who, "accum_pitch must be a multiple of 16");
+    return misaligned(who, "accum", 16, {accum});
 }
 
 }  // namespace
 
 extern "C" int rt_sample_priority(const rt_sample_priority_params* p, void* stream) {
-    if (!p) return fail("rt_sample_priority: null params");
-    if (!p->accum) return fail("rt_sample_priority: null accum");
-    if (!p->moments) return fail("rt_sample_priority: null moments");
-    if (!p->priority) return fail("rt_sample_priority: null priority");
-    if (image_refused("rt_sample_priority", p->width, p->height, p->accum, p->accum_pitch)) return 1;
-    if ((uintptr_t)p->moments & 7u) return fail("rt_sample_priority: moments must be 8-byte aligned");
-    if ((uintptr_t)p->priority & 3u) return fail("rt_sample_priority: priority must be 4-byte aligned");
+    const char* const who = "rt_sample_priority";
+    if (!p) return refuse(who, "null params");
+    if (!p->accum) return refuse(who, "null accum");
+    if (!p->moments) return refuse(who, "null moments");
+    if (!p->priority) return refuse(who, "null priority");
+    if (accum_refused(who, p->width, p->height, p->accum, p->accum_pitch)) return 1;
+    if (misaligned(who, "moments", 8, {p->moments}) || misaligned(who, "priority", 4, {p->priority})) return 1;
     const uint64_t n = (uint64_t)p->width * (uint64_t)p->height;
-    const uint64_t accum_bytes = (uint64_t)(p->height - 1) * p->accum_pitch + (uint64_t)p->width * 16;
-    if (overlap(p->priority, n * 4, p->accum, accum_bytes)) return fail("rt_sample_priority: priority must not overlap accum");
-    if (overlap(p->priority, n * 4, p->moments, n * 8)) return fail("rt_sample_priority: priority must not overlap moments");
+    const uint64_t accum_bytes = surface_bytes(p->height, p->accum_pitch, (uint64_t)p->width * 16);
+    if (overlap(p->priority, n * 4, p->accum, accum_bytes)) return refuse(who, "priority must not overlap accum");
+    if (overlap(p->priority, n * 4, p->moments, n * 8)) return refuse(who, "priority must not overlap moments");
     hipLaunchKernelGGL(priority_kernel, image_grid(p->width, p->height), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const char*>(p->accum), p->accum_pitch, reinterpret_cast<const float2*>(p->moments),
                        p->priority, p->width, p->height);
-    return hip_error("rt_sample_priority", "launch failed", hipGetLastError());
+    return launch_refused(who);
 }
 
 extern "C" int rt_sample_resolve(const rt_sample_resolve_params* p, void* stream) {
-    if (!p) return fail("rt_sample_resolve: null params");
-    if (!p->accum) return fail("rt_sample_resolve: null accum");
-    if (!p->out) return fail("rt_sample_resolve: null out");
-    if (image_refused("rt_sample_resolve", p->width, p->height, p->accum, p->accum_pitch)) return 1;
+    const char* const who = "rt_sample_resolve";
+    if (!p) return refuse(who, "null params");
+    if (!p->accum) return refuse(who, "null accum");
+    if (!p->out) return refuse(who, "null out");
+    if (accum_refused(who, p->width, p->height, p->accum, p->accum_pitch)) return 1;
+    if (pitch_refused(who, "out_pitch", p->out_pitch, p->width)) return 1;
+    if (p->out_pitch & 15u) return refuse(who, "out_pitch must be a multiple of 16");
+    if (misaligned(who, "out", 16, {p->out})) return 1;
     const uint64_t row = (uint64_t)p->width * 16;
-    if (p->out_pitch < row) return fail("rt_sample_resolve: out_pitch smaller than width * 16");
-    if (p->out_pitch & 15u) return fail("rt_sample_resolve: out_pitch must be a multiple of 16");
-    if ((uintptr_t)p->out & 15u) return fail("rt_sample_resolve: out must be 16-byte aligned");
-    if (overlap(p->out, (uint64_t)(p->height - 1) * p->out_pitch + row, p->accum, (uint64_t)(p->height - 1) * p->accum_pitch + row))
-        return fail("rt_sample_resolve: out must not overlap accum");
+    if (overlap(p->out, surface_bytes(p->height, p->out_pitch, row), p->accum, surface_bytes(p->height, p->accum_pitch, row)))
+        return refuse(who, "out must not overlap accum");
     hipLaunchKernelGGL(resolve_kernel, image_grid(p->width, p->height), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const char*>(p->accum), p->accum_pitch, static_cast<char*>(p->out), p->out_pitch, p->width,
                        p->height);
-    return hip_error("rt_sample_resolve", "launch failed", hipGetLastError());
+    return launch_refused(who);
 }
 
 extern "C" size_t rt_sample_plan_scratch_bytes(int width, int height) {
@@ -199,26 +175,25 @@ extern "C" size_t rt_sample_plan_scratch_bytes(int width, int height) {
 
 extern "C" int rt_sample_plan(const rt_sample_plan_params* p, void* stream) {
     const char* const who = "rt_sample_plan";
-    if (!p) return fail("rt_sample_plan: null params");
-    if (!p->priority) return fail("rt_sample_plan: null priority");
-    if (!p->pixels) return fail("rt_sample_plan: null pixels");
-    if (!p->samples) return fail("rt_sample_plan: null samples");
-    if (!p->scratch) return fail("rt_sample_plan: null scratch");
-    if (p->width <= 0 || p->height <= 0) return fail("rt_sample_plan: width and height must be > 0");
+    if (!p) return refuse(who, "null params");
+    if (!p->priority) return refuse(who, "null priority");
+    if (!p->pixels) return refuse(who, "null pixels");
+    if (!p->samples) return refuse(who, "null samples");
+    if (!p->scratch) return refuse(who, "null scratch");
+    if (size_refused(who, p->width, p->height)) return 1;
     const int64_t P = (int64_t)p->width * p->height;
-    if (P > kMaxPixels) return fail("rt_sample_plan: more than 2^30 pixels");
-    if (p->reserved != 0) return fail("rt_sample_plan: reserved must be 0");
-    if (p->max_samples < 1 || p->max_samples > 4095) return fail("rt_sample_plan: max_samples must be 1..4095");
-    if (p->min_samples < 0 || p->min_samples > p->max_samples) return fail("rt_sample_plan: min_samples must be 0..max_samples");
-    if (!(p->scale > 0.0f) || !(p->scale <= FLT_MAX)) return fail("rt_sample_plan: scale must be > 0 and finite");
-    if (p->budget < (int64_t)p->min_samples * P) return fail("rt_sample_plan: budget smaller than min_samples * width * height");
-    if ((uintptr_t)p->scratch & 15u) return fail("rt_sample_plan: scratch must be 16-byte aligned");
-    if ((uintptr_t)p->total & 7u) return fail("rt_sample_plan: total must be 8-byte aligned");
-    if (((uintptr_t)p->priority | (uintptr_t)p->pixels) & 3u) return fail("rt_sample_plan: priority and pixels must be 4-byte aligned");
-    if ((uintptr_t)p->samples & 1u) return fail("rt_sample_plan: samples must be 2-byte aligned");
+    if (P > kMaxPixels) return refuse(who, "more than 2^30 pixels");
+    if (p->reserved != 0) return refuse(who, "reserved must be 0");
+    if (p->max_samples < 1 || p->max_samples > 4095) return refuse(who, "max_samples must be 1..4095");
+    if (p->min_samples < 0 || p->min_samples > p->max_samples) return refuse(who, "min_samples must be 0..max_samples");
+    if (!finite_above(p->scale, 0.0f)) return refuse(who, "scale must be > 0 and finite");
+    if (p->budget < (int64_t)p->min_samples * P) return refuse(who, "budget smaller than min_samples * width * height");
+    if (misaligned(who, "scratch", 16, {p->scratch}) || misaligned(who, "total", 8, {p->total}) ||
+        misaligned(who, "priority and pixels", 4, {p->priority, p->pixels}) || misaligned(who, "samples", 2, {p->samples}))
+        return 1;
     const size_t n = (size_t)P;
     const PlanLayout l = plan_layout(n);
-    if (p->scratch_bytes < l.end) return fail("rt_sample_plan: scratch too small (rt_sample_plan_scratch_bytes)");
+    if (p->scratch_bytes < l.end) return refuse(who, "scratch too small (rt_sample_plan_scratch_bytes)");
     const struct {
         const char* name;
         const void* ptr;
@@ -227,11 +202,8 @@ extern "C" int rt_sample_plan(const rt_sample_plan_params* p, void* stream) {
                  {"total", p->total, 8},           {"scratch", p->scratch, l.end}};
     for (int i = 0; i < 5; i++)
         for (int j = i + 1; j < 5; j++)
-            if (overlap(bufs[i].ptr, bufs[i].bytes, bufs[j].ptr, bufs[j].bytes)) {
-                char msg[120];
-                snprintf(msg, sizeof msg, "rt_sample_plan: %s must not overlap %s", bufs[i].name, bufs[j].name);
-                return fail(msg);
-            }
+            if (overlap(bufs[i].ptr, bufs[i].bytes, bufs[j].ptr, bufs[j].bytes))
+                return refuse(who, std::string(bufs[i].name) + " must not overlap " + bufs[j].name);
 
     const hipStream_t st = (hipStream_t)stream;
     char* const scratch = static_cast<char*>(p->scratch);
@@ -242,24 +214,24 @@ extern "C" int rt_sample_plan(const rt_sample_plan_params* p, void* stream) {
     int end_bit = 0;  // the key max_samples - n_p is at most max_samples
     while ((p->max_samples >> end_bit) != 0) end_bit++;
     size_t sort_bytes = 0;
-    if (hip_error(who, "radix sort size query",
+    if (hip_refused(who, "radix sort size query",
                   hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, p->samples, values, p->pixels, (int)n, 0, end_bit, st)))
         return 1;
-    if (sort_bytes > l.sort_bound) return fail("rt_sample_plan: the radix sort asks for more storage than rt_sample_plan_scratch_bytes bounds");
+    if (sort_bytes > l.sort_bound) return refuse(who, "the radix sort asks for more storage than rt_sample_plan_scratch_bytes bounds");
 
-    if (hip_error(who, "hipMemsetAsync", hipMemsetAsync(cells, 0, 16, st))) return 1;
-    if (p->total && hip_error(who, "hipMemsetAsync", hipMemsetAsync(p->total, 0, 8, st))) return 1;
+    if (hip_refused(who, "hipMemsetAsync", hipMemsetAsync(cells, 0, 16, st))) return 1;
+    if (p->total && hip_refused(who, "hipMemsetAsync", hipMemsetAsync(p->total, 0, 8, st))) return 1;
     const dim3 grid((unsigned)((n + 255) / 256));
     hipLaunchKernelGGL(quantise_sum, grid, dim3(256), 0, st, p->priority, (uint32_t)n, p->scale, cells);
-    if (hip_error(who, "quantise_sum launch", hipGetLastError())) return 1;
+    if (hip_refused(who, "quantise_sum launch", hipGetLastError())) return 1;
     hipLaunchKernelGGL(plan_keys, grid, dim3(256), 0, st, p->priority, p->width, p->height, p->scale,
                        (unsigned long long)(p->budget - (int64_t)p->min_samples * P), (uint32_t)p->min_samples,
                        (uint32_t)p->max_samples, cells, keys, values, total);
-    if (hip_error(who, "plan_keys launch", hipGetLastError())) return 1;
-    if (hip_error(who, "radix sort",
+    if (hip_refused(who, "plan_keys launch", hipGetLastError())) return 1;
+    if (hip_refused(who, "radix sort",
                   hipcub::DeviceRadixSort::SortPairs(scratch + l.sort, sort_bytes, keys, p->samples, values, p->pixels, (int)n, 0,
                                                      end_bit, st)))
         return 1;
     hipLaunchKernelGGL(keys_to_counts, grid, dim3(256), 0, st, p->samples, (uint32_t)n, (uint32_t)p->max_samples);
-    return hip_error(who, "keys_to_counts launch", hipGetLastError());
+    return hip_refused(who, "keys_to_counts launch", hipGetLastError());
 }

@@ -21,9 +21,8 @@
 #include <numeric>
 #include <vector>
 
+#include "mirror.h"  // rt_internal_set_error
 #include "rt_abi.h"
-
-void rt_internal_set_error(const char* msg);
 
 static int64_t frame_tiles(int width, int height) {
     return (int64_t)((width + 15) / 16) * (int64_t)((height + 15) / 16);
