@@ -159,6 +159,16 @@ class DenoiseVarianceParams(ctypes.Structure):
                 ("sigma_lum", ctypes.c_float), ("min_history", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class UpsampleParams(ctypes.Structure):
+    """rt_upsample_params (rt_abi.h)."""
+    _fields_ = [("low_surface", ctypes.c_void_p), ("low_pitch", ctypes.c_uint64), ("low_hits", ctypes.c_void_p),
+                ("low_width", ctypes.c_int32), ("low_height", ctypes.c_int32), ("scale", ctypes.c_int32),
+                ("material_count", ctypes.c_int32), ("hits", ctypes.c_void_p), ("materials", ctypes.c_void_p),
+                ("out", ctypes.c_void_p), ("out_pitch", ctypes.c_uint64), ("scratch", ctypes.c_void_p),
+                ("scratch_bytes", ctypes.c_uint64), ("normal_power_log2", ctypes.c_int32), ("sigma_plane", ctypes.c_float),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class SamplePixelsParams(ctypes.Structure):
     """rt_sample_pixels_params (rt_abi.h)."""
     _fields_ = [("pixels", ctypes.c_void_p), ("samples", ctypes.c_void_p), ("count", ctypes.c_int64), ("rng", ctypes.c_void_p),
@@ -212,6 +222,10 @@ assert ctypes.sizeof(RadianceParams) == 48
 # the defaults rt_denoise_variance substitutes (csrc/denoise_variance.hip; profiles/variance_quality.txt)
 DENOISE_VARIANCE_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_plane": 0.03, "sigma_lum": 4.0, "min_history": 4.0}
 assert ctypes.sizeof(MomentsParams) == 64 and ctypes.sizeof(DenoiseVarianceParams) == 136
+UPSAMPLE_DEFAULT = -1  # RT_UPSAMPLE_DEFAULT: in a filter parameter of rt_upsample, the measured default
+# the defaults rt_upsample substitutes (csrc/upsample.hip; profiles/upsample_quality.txt)
+UPSAMPLE_DEFAULTS = {"normal_power_log2": 0, "sigma_plane": 0.03}
+assert ctypes.sizeof(UpsampleParams) == 104
 
 # name -> (restype, argtypes); every symbol include/rt_abi.h declares.
 _P, _I, _U32, _U64, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_size_t
@@ -231,6 +245,8 @@ SIGNATURES = {
     "rt_moments": (_I, [ctypes.POINTER(MomentsParams), _P]),
     "rt_denoise_variance_scratch_bytes": (_SZ, [_I, _I]),
     "rt_denoise_variance": (_I, [ctypes.POINTER(DenoiseVarianceParams), _P]),
+    "rt_upsample_scratch_bytes": (_SZ, [_I, _I]),
+    "rt_upsample": (_I, [ctypes.POINTER(UpsampleParams), _P]),
     "rt_sample_pixels": (_I, [ctypes.POINTER(SamplePixelsParams), _P, _P]),
     "rt_sample_priority": (_I, [ctypes.POINTER(SamplePriorityParams), _P]),
     "rt_sample_plan_scratch_bytes": (_SZ, [_I, _I]),
@@ -1305,6 +1321,66 @@ def denoise_variance(scene, surface, width, height, hits=None, moments=None, his
                              iterations, normal_power_log2, sigma_plane, sigma_lum, min_history, stream)
 
 
+def upsample_scratch_bytes(low_width, low_height):
+    """rt_upsample_scratch_bytes: bytes of scratch rt_upsample needs for a low frame of low_width x low_height pixels."""
+    return int(lib().rt_upsample_scratch_bytes(int(low_width), int(low_height)))
+
+
+def _upsample(low_surface, low_hits, hits, materials, low_width, low_height, scale, out, scratch, normal_power_log2,
+              sigma_plane, stream):
+    lw, lh, s = int(low_width), int(low_height), int(scale)
+    w, h = lw * s, lh * s
+    assert _is_surface(low_surface, lw, lh) and _is_hits(low_hits, lw, lh) and _is_hits(hits, w, h)
+    need = upsample_scratch_bytes(lw, lh)
+    with _allocating_on(stream):  # as _denoise: what is allocated here is allocated on the stream the kernels run on
+        if out is None:
+            out = alloc_surface(w, h, device=low_surface.device)
+        if scratch is None:
+            scratch = torch.empty((need // 4,), dtype=torch.float32, device=low_surface.device)
+    assert _is_surface(out, w, h)
+    assert scratch.is_cuda and scratch.is_contiguous()
+    p = UpsampleParams()
+    p.low_surface, p.low_pitch = low_surface.data_ptr(), low_surface.stride(0) * 4
+    p.low_hits, p.hits = low_hits.data_ptr(), hits.data_ptr()
+    p.low_width, p.low_height, p.scale = lw, lh, s
+    p.materials, p.material_count = _materials_of(materials)
+    p.out, p.out_pitch = out.data_ptr(), out.stride(0) * 4
+    p.scratch, p.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
+    p.normal_power_log2, p.sigma_plane = int(normal_power_log2), float(sigma_plane)
+    _check(lib().rt_upsample(ctypes.byref(p), _stream_ptr(stream)), "rt_upsample")
+    return out
+
+
+def upsample_raw(low_surface, low_hits, hits, materials, low_width, low_height, scale, out=None, scratch=None,
+                 normal_power_log2=UPSAMPLE_DEFAULT, sigma_plane=UPSAMPLE_DEFAULT, stream=None):
+    """rt_upsample on tensors only: `low_surface` a pitched float4 surface of low_width x low_height pixels, `low_hits`
+    and `hits` float32 [N, 12] tensors of rt_hit rows of one camera at the low size and at the output size
+    (scale * low_width x scale * low_height; scale 2, 3 or 4), `materials` a float32 CUDA tensor [M, 16] of
+    GPUMaterial rows (M may be 0).  Returns `out`, a surface of the output size (a new one when None; it may overlap
+    none of the inputs).  `scratch`: any contiguous CUDA tensor of at least upsample_scratch_bytes(low_width,
+    low_height) bytes, contents irrelevant (allocated when None).  A filter parameter left at UPSAMPLE_DEFAULT takes
+    the library's default (UPSAMPLE_DEFAULTS).  Stream-ordered on `stream` (default: torch's current stream); tensors
+    allocated here are allocated on that stream, tensors passed in must be safe to use on it."""
+    assert isinstance(materials, torch.Tensor)
+    return _upsample(low_surface, low_hits, hits, materials, low_width, low_height, scale, out, scratch,
+                     normal_power_log2, sigma_plane, stream)
+
+
+def upsample(scene, low_surface, low_width, low_height, scale, low_hits=None, hits=None, out=None, scratch=None,
+             normal_power_log2=UPSAMPLE_DEFAULT, sigma_plane=UPSAMPLE_DEFAULT, stream=None):
+    """A frame of scale * low_width x scale * low_height pixels from a frame of an uploaded Scene rendered at low_width x
+    low_height: rt_upsample guided by the camera's first-hit records at both sizes (`low_hits`, `hits`; each traced
+    with trace_camera on the call's stream when None -- the uploaded camera serves both sizes, its aspect being the
+    same) and the scene's materials.  Returns `out` (a new surface when None)."""
+    lw, lh, s = int(low_width), int(low_height), int(scale)
+    with _allocating_on(stream):
+        if low_hits is None:
+            low_hits = trace_camera(scene, lw, lh, stream=stream)
+        if hits is None:
+            hits = trace_camera(scene, lw * s, lh * s, stream=stream)
+    return _upsample(low_surface, low_hits, hits, scene, lw, lh, s, out, scratch, normal_power_log2, sigma_plane, stream)
+
+
 class VarianceAccumulator:
     """The per-frame chain of the variance-steered filter: rt_reproject on the colour (a TemporalAccumulator),
     rt_moments on the new frame, rt_reproject on the moments with a history of their own, rt_denoise_variance on
@@ -1627,6 +1703,24 @@ class RayTracer:
         self.scene.set_viewport(self.width, self.height)
         self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
         return denoise(self.scene, self.surface, self.width, self.height, **kw)
+
+    def upsampled(self, scale=2, denoise=False, **kw):
+        """The current frame as a new pitched surface of scale * width x scale * height pixels (module-level
+        upsample(); **kw are its filter parameters, low_hits, hits, scratch, stream).  With denoise=True the frame
+        goes through rt_denoise (its defaults) first.  Uploads the scene like process(); `surface`, `last_frame`, the
+        RNG states and the frame index are left alone."""
+        assert "out" not in kw, "RayTracer.upsampled returns a new surface"
+        self.scene.set_viewport(self.width, self.height)
+        self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
+        stream = kw.get("stream")
+        with _allocating_on(stream):
+            if kw.get("low_hits") is None:
+                kw["low_hits"] = trace_camera(self.scene, self.width, self.height, stream=stream)
+        low = self.surface
+        if denoise:
+            low = _denoise(low, kw["low_hits"], self.scene, self.width, self.height, None, None, DENOISE_DEFAULT,
+                           DENOISE_DEFAULT, DENOISE_DEFAULT, DENOISE_DEFAULT, stream)
+        return upsample(self.scene, low, self.width, self.height, scale, **kw)
 
     def ao(self, radius, **kw):
         """The ambient-occlusion image [H, W] of the current camera and size (module-level ambient_occlusion();

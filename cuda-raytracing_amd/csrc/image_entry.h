@@ -1,6 +1,6 @@
 // image_entry.h -- what the entry points share on the host: how a call refuses ("who: what" through
 // rt_internal_set_error, return value 1) and the checks of a pitched float4 image, each written once.  Used by the
-// image-space calls (denoise.hip, denoise_variance.hip, reproject.hip, sample_plan.hip, image.hip) and by the
+// image-space calls (denoise.hip, denoise_variance.hip, reproject.hip, sample_plan.hip, upsample.hip, image.hip) and by the
 // ray-batch calls of rt_kernel.hip.  A check whose wording belongs to one call stays a line of that call.
 #pragma once
 
@@ -61,11 +61,14 @@ inline int size_refused(const char* who, int width, int height) {
     return (width <= 0 || height <= 0) ? refuse(who, "width and height must be > 0") : 0;
 }
 // The caps of the filters' launch grids (a row of blocks per 4 or 8 pixel rows in grid.y, at most 65,535) and scratch;
-// `family` names the constants the message quotes: "DENOISE" or "REPROJECT", which rt_abi.h defines alike.
-inline int caps_refused(const char* who, int width, int height, const char* family) {
-    static_assert(RT_REPROJECT_MAX_HEIGHT == RT_DENOISE_MAX_HEIGHT && RT_REPROJECT_MAX_PIXELS == RT_DENOISE_MAX_PIXELS, "one set of caps");
+// `family` names the constants the message quotes: "DENOISE", "REPROJECT" or "UPSAMPLE", which rt_abi.h defines alike.
+// The sizes are 64 bits wide for rt_upsample, whose capped size is a product (scale * low size, below 2^34).
+inline int caps_refused(const char* who, int64_t width, int64_t height, const char* family) {
+    static_assert(RT_REPROJECT_MAX_HEIGHT == RT_DENOISE_MAX_HEIGHT && RT_REPROJECT_MAX_PIXELS == RT_DENOISE_MAX_PIXELS &&
+                      RT_UPSAMPLE_MAX_HEIGHT == RT_DENOISE_MAX_HEIGHT && RT_UPSAMPLE_MAX_PIXELS == RT_DENOISE_MAX_PIXELS,
+                  "one set of caps");
     if (height > RT_DENOISE_MAX_HEIGHT) return refuse(who, std::string("height above RT_") + family + "_MAX_HEIGHT");
-    if ((int64_t)width * height > RT_DENOISE_MAX_PIXELS) return refuse(who, std::string("more than RT_") + family + "_MAX_PIXELS pixels");
+    if (width * height > RT_DENOISE_MAX_PIXELS) return refuse(who, std::string("more than RT_") + family + "_MAX_PIXELS pixels");
     return 0;
 }
 // a row of float4 pixels must fit the pitch called `name`

@@ -812,6 +812,93 @@ size_t rt_denoise_variance_scratch_bytes(int width, int height);
 int rt_denoise_variance(const rt_denoise_variance_params* params, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Upsampling: a frame rendered at 1/scale of the size in each direction (a quarter to a sixteenth of the paths)
+ * brought to the full size, guided by the first-hit records at both sizes:
+ *
+ *   rt_render(low_width, low_height) -> rt_trace_rays camera mode at the low size and at the output size
+ *   [-> rt_denoise on the low frame] -> rt_upsample.
+ *
+ * One camera serves both sizes: GPUCamera depends on the viewport through aspect = width / height only, and
+ * (float)(s*w) / (float)(s*h) is the same correctly rounded quotient, so nothing is uploaded again between the calls.
+ * A joint-bilateral gather on albedo-divided colour, as rt_denoise's: the low colours are divided by their own first
+ * hit's albedo and the result is multiplied by the *output* pixel's, so texture edges come out at the full resolution.
+ *
+ * The arithmetic is fixed as rt_denoise's is (fp32, no contraction, IEEE division, only + - * /, fmaxf, fabsf and
+ * comparisons), so that tests/upsample_ref.py restates it bit for bit.  tag (0 for a miss), the floor-clamped albedo
+ * a (1 for a miss), dot and the guide weights wn and wz are rt_denoise's (steps 1 and 2 of its block above), with the
+ * *output* pixel as the centre p of wn and wz and the low pixel as the tap q.  Low pixel q has tag_q and colour
+ * c_q = low_surface[q].rgb / a_q.  Output pixel P = (X, Y) has record hits[Y * width + X], tag_P and a_P.  With
+ * s = scale:
+ *
+ *  1. Footprint: ix = 2X + 1 - s (an int, may be negative); x0 = floor(ix / 2s) (floor division: -1 for a negative
+ *     ix); rx = ix - 2s*x0; tx = (float)rx / (float)(2s); wx = {1.0f - tx, tx}.  The same in y.
+ *  2. Guide g(P, q): when tag_P == 0, 1 if tag_q == 0, else 0; when tag_P != 0, 0 if tag_q == 0, else wn * wz
+ *     (wn squared normal_power_log2 times, wz squared once; with sigma_plane * t_P in wz).
+ *  3. Stage 1: for j = 0..1 (outer), i = 0..1 (inner), q = (x0 + i, y0 + j), skipping q outside the low image and
+ *     c_q.rgb not finite: w = (wy[j] * wx[i]) * g; if w > 0: sum += c_q * w, wsum += w.
+ *  4. Stage 2, only if wsum > 0 is false after stage 1: for j = 0..3, i = 0..3, q = (x0 - 1 + i, y0 - 1 + j), the
+ *     same skips, w = g; if w > 0: sum += c_q * w, wsum += w.
+ *  5. c = wsum > 0 ? sum / wsum : c_near with near = (X / s, Y / s) (stage 3; a c_near that is not finite passes
+ *     through).  out.rgb = c * a_P, out.w = low_surface[near].w.
+ *
+ * A tap is added only if w > 0, never as a zero.  Why three stages: stage 1 is bilinear interpolation wherever the
+ * guide agrees; an output pixel whose four low neighbours all lie on other surfaces (a thin object, a silhouette)
+ * looks for its own surface one ring further out, where the bilinear weights would be extrapolating, hence the guide
+ * alone; and a pixel with no usable low pixel nearby at all still gets a colour.
+ *
+ * Preconditions: both hit buffers come from the same camera (the positions are compared in world space); t_P == 0
+ * gives wz = 0 (inf or NaN -> 0) for every tap, and with it stage 3.
+ * ------------------------------------------------------------------------------------- */
+#define RT_UPSAMPLE_DEFAULT (-1)   /* in either filter parameter: the measured default */
+#define RT_UPSAMPLE_MAX_HEIGHT RT_DENOISE_MAX_HEIGHT  /* of the output: the launch grid holds a row of blocks per 4 pixel rows */
+#define RT_UPSAMPLE_MAX_PIXELS RT_DENOISE_MAX_PIXELS  /* of the output */
+
+typedef struct rt_upsample_params {
+    const void* low_surface;       /* DEVICE pitched float4 frame of low_width x low_height pixels */
+    uint64_t low_pitch;            /* bytes per row of low_surface: >= low_width * 16, a multiple of 16 */
+    const rt_hit* low_hits;        /* DEVICE low_width * low_height records of rt_trace_rays' camera mode */
+    int32_t low_width, low_height; /* > 0 */
+    int32_t scale;                 /* 2, 3 or 4: the output is scale * low_width x scale * low_height pixels, height <=
+                                      RT_UPSAMPLE_MAX_HEIGHT, width * height <= RT_UPSAMPLE_MAX_PIXELS */
+    int32_t material_count;
+    const rt_hit* hits;            /* DEVICE width * height records of camera mode at the output size, same camera */
+    const GPUMaterial* materials;  /* DEVICE (GPUScene.gpu_materials); may be NULL when material_count is 0 */
+    void* out;                     /* DEVICE pitched float4 result at the output size; row padding is never written */
+    uint64_t out_pitch;            /* >= width * 16, a multiple of 16 */
+    void* scratch;                 /* DEVICE, rt_upsample_scratch_bytes(low_width, low_height); contents irrelevant */
+    uint64_t scratch_bytes;
+    /* Filter parameters.  RT_UPSAMPLE_DEFAULT (-1, -1.0f) selects the default (profiles/upsample_quality.txt). */
+    int32_t normal_power_log2;     /* 0..8 (0): the normal weight is cos^(2^this), cos clamped at 0 */
+    float sigma_plane;             /* > 0, finite (0.03): tolerated distance from P's tangent plane, as a fraction of t_P */
+    int32_t flags;                 /* must be 0 */
+    int32_t reserved;              /* must be 0 */
+} rt_upsample_params;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_upsample_params) == 104 && offsetof(rt_upsample_params, low_surface) == 0 &&
+              offsetof(rt_upsample_params, low_pitch) == 8 && offsetof(rt_upsample_params, low_hits) == 16 &&
+              offsetof(rt_upsample_params, low_width) == 24 && offsetof(rt_upsample_params, low_height) == 28 &&
+              offsetof(rt_upsample_params, scale) == 32 && offsetof(rt_upsample_params, material_count) == 36 &&
+              offsetof(rt_upsample_params, hits) == 40 && offsetof(rt_upsample_params, materials) == 48 &&
+              offsetof(rt_upsample_params, out) == 56 && offsetof(rt_upsample_params, out_pitch) == 64 &&
+              offsetof(rt_upsample_params, scratch) == 72 && offsetof(rt_upsample_params, scratch_bytes) == 80 &&
+              offsetof(rt_upsample_params, normal_power_log2) == 88 && offsetof(rt_upsample_params, sigma_plane) == 92 &&
+              offsetof(rt_upsample_params, flags) == 96 && offsetof(rt_upsample_params, reserved) == 100,
+              "rt_upsample_params");
+#endif
+
+/* Bytes of scratch rt_upsample needs for a low frame of low_width x low_height pixels (48 per low pixel: normal,
+ * position and tag, albedo-divided colour); 0 for a size <= 0.  Monotone in both arguments. */
+size_t rt_upsample_scratch_bytes(int low_width, int low_height);
+/* Upsample on `stream` (a hipStream_t, NULL = null stream): stream-ordered, no synchronisation, no allocation; two
+ * kernel launches.  Every argument is checked on the host before the first launch, in this order, the first fault
+ * reported: NULL pointers (params, low_surface, low_hits, hits, out, scratch); low sizes <= 0 and the scale; the caps,
+ * on the output size; materials; pitches; alignment (16 bytes, every buffer); scratch too small; overlaps; flags and
+ * reserved != 0; parameters out of range.  `out` must not overlap low_surface, low_hits, hits, scratch or the material
+ * table.  Returns 0 or an error code with rt_last_error(). */
+int rt_upsample(const rt_upsample_params* params, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Adaptive sampling: per-pixel sample budgets.  Four calls, each usable alone:
  *
  *   rt_sample_pixels    trace samples[i] more of the renderer's own samples for pixel pixels[i], into an undivided

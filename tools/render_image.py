@@ -8,6 +8,7 @@
     python tools/render_image.py --temporal K [--variance]
     python tools/render_image.py --panorama W
     python tools/render_image.py --adaptive ROUNDS
+    python tools/render_image.py --upsample S [--denoise]
 
 --aov PREFIX also writes the first-hit images of the same camera (rt.gbuffer: pixel centres, no jitter) as
 PREFIX_normal.pfm (normal * 0.5 + 0.5), PREFIX_depth.pfm (hit distance, inf on a miss) and PREFIX_albedo.pfm.
@@ -24,6 +25,9 @@ position at the config's spp and bounces (rt.panorama: rt_radiance along rt.pano
 --adaptive ROUNDS also writes OUT_adaptive.pfm / .ppm and OUT_samples.pfm: rt.AdaptiveSampler at the config's camera --
 a warm-up of 2 samples a pixel, then ROUNDS rounds that each spend at most the config's spp per pixel where the relative
 variance of the mean is largest -- and its samples per pixel as a linear grey image.
+--upsample S (2, 3 or 4) renders everything above at 1/S of the config's size in each direction (a size that S does not
+divide is refused) and also writes OUT_upsampled.pfm / .ppm at the config's size: rt.upsample of the last frame, guided
+by the camera's first-hit records at both sizes.  With --denoise the low frame goes through rt.denoise first.
 """
 import argparse
 import os
@@ -59,10 +63,15 @@ def main():
     ap.add_argument("--variance", action="store_true", help="with --temporal: also filter (rt_denoise_variance)")
     ap.add_argument("--panorama", type=int, default=None, metavar="W")
     ap.add_argument("--adaptive", type=int, default=None, metavar="ROUNDS")
+    ap.add_argument("--upsample", type=int, default=None, metavar="S", choices=(2, 3, 4))
     args = ap.parse_args()
     assert not args.variance or args.temporal is not None, "--variance needs --temporal K"
     rt = G.load_package()
     scene_name, W, H, SPP, BOUNCES, _ = bench.CONFIGS[args.config]
+    if args.upsample is not None:
+        if W % args.upsample or H % args.upsample:
+            sys.exit(f"--upsample {args.upsample} does not divide {W}x{H}")
+        W, H = W // args.upsample, H // args.upsample
     torch.cuda.set_device(0)
     scene = rt.Scene()
     scene.setup(scene_name)
@@ -78,11 +87,18 @@ def main():
     rt.write_pfm(args.out + ".pfm", final, W, H)
     rt.write_ppm(args.out + ".ppm", rt.tonemap(final, W, H))
     print(f"wrote {args.out}.pfm / .ppm ({W}x{H}, {args.frames} frames x {SPP} spp)")
+    clean = None
     if args.denoise:
         clean = rt.denoise(scene, final, W, H)
         rt.write_pfm(args.out + "_denoised.pfm", clean, W, H)
         rt.write_ppm(args.out + "_denoised.ppm", rt.tonemap(clean, W, H))
         print(f"wrote {args.out}_denoised.pfm / .ppm")
+    if args.upsample is not None:
+        big = rt.upsample(scene, clean if clean is not None else final, W, H, args.upsample)
+        bw, bh = W * args.upsample, H * args.upsample
+        rt.write_pfm(args.out + "_upsampled.pfm", big, bw, bh)
+        rt.write_ppm(args.out + "_upsampled.ppm", rt.tonemap(big, bw, bh))
+        print(f"wrote {args.out}_upsampled.pfm / .ppm ({bw}x{bh} from {W}x{H}" + (", denoised first)" if clean is not None else ")"))
     if args.ao is not None:
         ao = rt.ambient_occlusion(scene, rt.trace_camera(scene, W, H), W, H, args.ao)
         pfm, ppm = ao_outputs(ao)
