@@ -6,7 +6,7 @@
 // (main_raytracing.cu:33-81) of any camera ray of the sub-tile visits, below the root, only subtrees of
 // those nodes.  The lean render kernels (rt_fast.h trav_begin_entry) start a camera ray from its record
 // instead of the root.  The same code runs on the host (tests: entry_host.cpp; tools/entry_probe.cpp) and in the builder
-// kernel (rt_kernel.hip entry_table_kernel), one lane per sub-tile.
+// kernel (entry_table.hip entry_table_kernel), one lane per sub-tile.
 //
 // A record is built from [root] by replacing an inner node by its children, right child first (the
 // reference pops first + 1 first), leaving out a child that is PROVEN missed:

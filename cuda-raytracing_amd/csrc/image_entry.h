@@ -1,7 +1,7 @@
 // image_entry.h -- what the entry points share on the host: how a call refuses ("who: what" through
 // rt_internal_set_error, return value 1) and the checks of a pitched float4 image, each written once.  Used by the
 // image-space calls (denoise.hip, denoise_variance.hip, reproject.hip, sample_plan.hip, upsample.hip, image.hip) and by the
-// ray-batch calls of rt_kernel.hip.  A check whose wording belongs to one call stays a line of that call.
+// ray-batch calls (rt_batch_calls.hip), rt_render.hip and rng_shard.hip.  A check whose wording belongs to one call stays a line of that call.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -415,50 +415,45 @@ std::mutex g_mutex;
 std::map<const void*, Entry> g_mirrors;  // keyed by the device BVH node array
 
 void release(Entry& e) {
-    rt_internal_forget_entry_table(e.dev.nodes);  // the entry table built over this node array (rt_kernel.hip)
+    rt_internal_forget_entry_table(e.dev.nodes);  // the entry table built over this node array (entry_table.hip)
     if (e.block) rt_free(e.block);
     e.block = nullptr;
 }
 }  // namespace
 
-int rt_internal_install_mirror(const GPUScene* s, const MirrorHost& m, bool owned, uint64_t fingerprint) {
-    const std::vector<float> lt = rt_ltris_device_layout(m.ltris);
-    // the parts in one block, each starting on a 256-B boundary (pairs of nodes and records on
-    // cache-line boundaries: mirror.h)
-    const std::vector<float>* parts[11] = {&m.nodes, &m.tris, &m.pairs, &m.tree, &lt, &m.spairs, &m.flat, &m.treelets, &m.quads,
+MirrorLayout::MirrorLayout(const MirrorHost& m) : ltris(rt_ltris_device_layout(m.ltris)) {
+    const std::vector<float>* parts[11] = {&m.nodes, &m.tris, &m.pairs, &m.tree, &ltris, &m.spairs, &m.flat, &m.treelets, &m.quads,
                                            &m.units, &m.face_leaf};
-    size_t off[11], total = 0;
+    bytes = 256;
     for (int i = 0; i < 11; i++) {
-        off[i] = total;
-        total += (parts[i]->size() * 4 + 255) & ~(size_t)255;
+        part[i] = parts[i]->data(), size[i] = parts[i]->size() * 4, offset[i] = bytes - 256;
+        bytes += (size[i] + 255) & ~(size_t)255;
     }
+    dev.node_count = (uint32_t)(m.nodes.size() / 8);
+    dev.depth = m.depth, dev.fast = m.fast, dev.screens = m.screens;
+}
+
+MirrorDevice MirrorLayout::at(const void* block) const {
+    const char* b = static_cast<const char*>(block);
+    auto p = [&](int i) -> const void* { return size[i] ? b + offset[i] : nullptr; };
+    MirrorDevice d = dev;
+    d.nodes = p(0), d.tris = b + offset[1], d.pairs = p(2), d.tree = p(3), d.ltris = p(4), d.spairs = p(5), d.flat = p(6);
+    d.treelets = p(7), d.quads = p(8), d.units = p(9), d.face_leaf = p(10);
+    return d;
+}
+
+int rt_internal_install_mirror(const GPUScene* s, const MirrorHost& m, bool owned, uint64_t fingerprint) {
+    const MirrorLayout lay(m);
     void* block = nullptr;
-    if (rt_malloc(&block, total + 256) != 0) return -1;
-    char* b = static_cast<char*>(block);
+    if (rt_malloc(&block, lay.bytes) != 0) return -1;
     for (int i = 0; i < 11; i++)
-        if (!parts[i]->empty() && rt_memcpy_h2d(b + off[i], parts[i]->data(), parts[i]->size() * 4) != 0) {
+        if (lay.size[i] && rt_memcpy_h2d(static_cast<char*>(block) + lay.offset[i], lay.part[i], lay.size[i]) != 0) {
             rt_free(block);
             return -1;
         }
-    auto at = [&](int i) -> const void* { return parts[i]->empty() ? nullptr : b + off[i]; };
-    Entry e{s->gpu_bvh_face_indices, s->gpu_vertices, s->gpu_faces, block, {}};
-    e.dev.nodes = at(0);
-    e.dev.tris = b + off[1];
-    e.dev.pairs = at(2);
-    e.dev.tree = at(3);
-    e.dev.ltris = at(4);
-    e.dev.spairs = at(5);
-    e.dev.flat = at(6);
-    e.dev.treelets = at(7);
-    e.dev.quads = at(8);
-    e.dev.units = at(9);
-    e.dev.face_leaf = at(10);
+    Entry e{s->gpu_bvh_face_indices, s->gpu_vertices, s->gpu_faces, block, lay.at(block)};
     static std::atomic<uint64_t> generation{0};
     e.dev.generation = ++generation;
-    e.dev.node_count = (uint32_t)(m.nodes.size() / 8);
-    e.dev.depth = m.depth;
-    e.dev.fast = m.fast;
-    e.dev.screens = m.screens;
     e.dev.owned = owned;
     e.dev.fingerprint = fingerprint;
     std::lock_guard<std::mutex> lock(g_mutex);

@@ -125,14 +125,28 @@ struct MirrorDevice {
     bool owned = true;         // built by rt_scene_upload, which forgets it before freeing the arrays
     uint64_t fingerprint = 0;  // foreign scenes: content hash of the arrays it was built from
 };
+// A mirror's eleven parts laid out in one device block, each part on a 256-B boundary (pairs of nodes and records on
+// cache-line boundaries, above): the caller allocates `bytes`, copies part[i] (size[i] bytes, 0 for an empty one) to
+// block + offset[i] in its own way, and at(block) is the device view -- every field but generation, owned and
+// fingerprint, which are the caller's.  Used by rt_internal_install_mirror and by foreign.hip's worker.
+struct MirrorLayout {
+    explicit MirrorLayout(const MirrorHost& m);
+    MirrorDevice at(const void* block) const;
+    const void* part[11];
+    size_t size[11], offset[11], bytes;
+
+private:
+    std::vector<float> ltris;  // rt_ltris_device_layout of the host's, the part that is not copied as it stands
+    MirrorDevice dev;          // the fields that are no addresses
+};
 // owned = false: a GPUScene filled by another host (the reference's Scene.cpp); the mirror is
-// then revalidated against `fingerprint` at every use (rt_kernel.hip foreign_mirror).
+// then revalidated against `fingerprint` at every use (foreign.hip foreign_frame).
 int rt_internal_install_mirror(const GPUScene* scene, const MirrorHost& m, bool owned = true,
                                uint64_t fingerprint = 0);  // 0 or -1 (rt_last_error)
 void rt_internal_forget_mirror(const void* gpu_nodes);
 bool rt_internal_lookup_mirror(const GPUScene* scene, MirrorDevice* out);
 
-// rt_kernel.hip: drops the camera rays' entry table (entry_frontier.h) built over a mirror's node array
+// entry_table.hip: drops the camera rays' entry table (entry_frontier.h) built over a mirror's node array
 void rt_internal_forget_entry_table(const void* mirror_nodes);
 
 void rt_internal_set_error(const char* msg);  // rt_last_error() text (rt_kernel.hip)

@@ -1,4 +1,4 @@
-// rt_common.h -- types shared by the render kernels (rt_kernel.hip, rt_wave.hip).
+// rt_common.h -- types shared by the render kernels (rt_fast_*.hip, rt_ref.hip) and the host units that launch them (rt_render.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -71,7 +71,7 @@ struct RenderArgs {
     //   clocks), 9-10 occupancy override (1 compiler's choice, 2 = 6, 3 = 7 waves per SIMD),
     //   11 per-wave clock records, 12 no split small steps, 13-15 split threshold, 16-19 XCD run
     //   length (xcd_block), 20 no twin quads, 21-23 twin rounds' cooperative weight, 24 no deferred leaf trees, 26 no lone-ray traversal, 27 the reference's node array instead of the
-    //   mirror's private one (rt_kernel.hip), 28 no big-leaf screens, 30 per-lane leaf-tree walk,
+    //   mirror's private one (rt_render.hip), 28 no big-leaf screens, 30 per-lane leaf-tree walk,
     //   31 subtree order.
     uint32_t tune;
 };

@@ -3,7 +3,7 @@
 // forms the camera ray of its pixel centre), runs GetRayHit's sphere loop and rtfast::trace exactly as
 // render_fast_body does (rt_fast_body.h), and writes one 48-byte hit record with the attributes shade_segment
 // computes -- no RNG, no shading, no sky, no surface.  The kernel frame, the variants and the launch are the
-// ray-batch scaffold's (rt_batch.h); rt_kernel.hip picks the variant (rt_trace_rays).
+// ray-batch scaffold's (rt_batch.h); rt_batch_calls.hip picks the variant (rt_trace_rays).
 #include "rt_batch.h"
 
 namespace rtk {

@@ -1,4 +1,4 @@
-// rt_render.h -- launchers of the render kernels, one family per translation unit (rt_kernel.hip chooses and
+// rt_render.h -- launchers of the render kernels, one family per translation unit (rt_render.hip chooses and
 // launches through the family table below; the families compile in parallel).  `stack` is the traversal stack
 // size of the instantiation (30, 40 or 64 entries), `mode` the MODE bits of render_fast_body (rt_fast_body.h;
 // both from rt_variant.h choose_variant).  Each returns hipErrorInvalidValue for a mode it does not hold.
@@ -46,7 +46,7 @@ hipError_t launch_ref_tracer(bool flat, const RenderArgs& a, int waves, int dept
 
 // The ray-query kernel (rt_query.hip, rt_trace_rays): one ray per lane through rtfast::trace, no shading.
 // `rays` null = camera mode (pixel centres of `cam`, width x height).  The mirror arrays are the ones a
-// render launch passes to trace (rt_kernel.hip).
+// render launch passes to trace (rt_batch_calls.hip query_scene).
 struct QueryArgs {
     const rt_ray* rays;
     rt_hit* hits;
@@ -128,7 +128,7 @@ struct ExperimentalKernels {
 // version bumped by hand when a field changes meaning, and the two sizes.  A plugin built against another
 // layout is refused at registration instead of reading a different struct (rt_exp_abi_version).
 constexpr uint32_t kExperimentalAbi = (3u << 24) ^ ((uint32_t)sizeof(RenderArgs) << 8) ^ (uint32_t)sizeof(ExperimentalKernels);
-// rt_kernel.hip: the registered table (nullptr until librt_hip_exp.so is loaded); a table whose `abi` is
+// rt_render.hip: the registered table (nullptr until librt_hip_exp.so is loaded); a table whose `abi` is
 // not this library's kExperimentalAbi is refused (rt_last_error says so, rt_experimental_loaded stays 0).
 void register_experimental_kernels(const ExperimentalKernels* k, uint32_t abi);
 const ExperimentalKernels* experimental_kernels();

@@ -1,6 +1,6 @@
 // rt_variant.h -- which instantiation of render_fast_body<STACK, STATS, MODE> (rt_fast_body.h) a frame runs: the
 // names of MODE's bits, of the RT_TUNE bits the host reads to choose, and choose_variant, the one statement of
-// that choice (rt_kernel.hip: rt_render, rt_trace_rays, rt_variant_host).  Host-only and free of HIP, so a
+// that choice (rt_render.hip rt_render, rt_batch_calls.hip query_scene, host_hooks.hip rt_variant_host).  Host-only and free of HIP, so a
 // plain C++ compiler can replay it (tests/test_variant_cpu.py pins it to the table of the if-chains it replaced).
 #pragma once
 
@@ -70,7 +70,7 @@ constexpr int kEntryStackExtra = 14;
 // of LDS per wave -- still fit 5 waves per SIMD and cover the 4-bunny scene's depth 28.
 // The deepest BVH any traversal kernel is launched on: the largest STACK is 64 entries and the walk needs depth + 2
 // (rtfast::Stack::put has no bound of its own -- a deeper tree would write past its arrays).  rt_render, rt_trace_rays,
-// rt_occluded and rt_ao refuse a deeper scene (rt_kernel.hip depth_refused) before anything is launched.
+// rt_occluded and rt_ao refuse a deeper scene (rt_kernel.hip depth_refused, rt_host.h) before anything is launched.
 constexpr int kMaxBvhDepth = 62;
 
 inline int variant_stack(int depth, int extra = 0) {
