@@ -326,6 +326,9 @@ SIGNATURES = {
     "rt_mirror_build_check": (_I, [_P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, ctypes.POINTER(ctypes.c_int)]),
     "rt_cluster_cull_host": (_I, [_P, _P, ctypes.c_float, _P]),
     "rt_twin_check_host": (_I, [_P, _P, _P]),
+    "rt_twin_check_bounds_host": (_I, [_P, _P, _P, _P]),
+    "rt_twin_visit_host": (None, [_P, _P, _P, ctypes.c_float, _P]),
+    "rt_scene_mirror_leaf_twin": (_I, [_P, _U32, _P]),
     "rt_variant_host": (None, [_P, _P]),
     "rt_family_has_mode_host": (_I, [_I, _I]),
     "rt_xorwow_jump_matrix": (_I, [_I, ctypes.POINTER(ctypes.c_uint32)]),
@@ -525,6 +528,14 @@ class Scene:
         _check(lib().rt_scene_mirror_twins(self.handle, q.ctypes.data, ctypes.byref(nq), u.ctypes.data, ctypes.byref(nu)),
                "rt_scene_mirror_twins")
         return q, u
+
+    def mirror_leaf_twin(self, first):
+        """The twin record (mirror.h pairs) of the big leaf whose first leaf-ordered record is `first`: 12 float32
+        (KD, KE, KDD, KDD1, lo.xyz, 0, hi.xyz, 0)."""
+        import numpy as np
+        rec = np.zeros(12, dtype=np.float32)
+        _check(lib().rt_scene_mirror_leaf_twin(self.handle, int(first), rec.ctypes.data), "rt_scene_mirror_leaf_twin")
+        return rec
 
     def materials(self):
         """Host copy of the GPUMaterial array as (M, 16) float32: albedo 0-3, emissive 4-7, specular 8-11,

@@ -19,8 +19,12 @@ extern "C" int rt_experimental_loaded() { return rtk::experimental_kernels() ? 1
 // The twin test (rt_fast.h twin_rejected) on the host, for tests/test_scene.py: triangle record `rec`
 // (mirror.h tris) and its twin (v0, e2, e1) under glm's test (test_triangle's operation order) for the
 // ray (o, nd); bit 0: twin_rejected, bit 1: the twin passes glm's predicate, bit 2: A passes it.
-extern "C" int rt_twin_check_host(const float rec[12], const float o[3], const float nd[3]) {
+// With `bounds` = (KD, KE, DN) the hoisted form decides instead (twin_rejected_pre on those bounds, as the
+// kernels call it), and bit 3 says that the packed evaluation of the shared-leaf loop (quad_test's sequence on
+// an f2 holding this triangle in either half) and the scalar one disagree.
+static int twin_check(const float rec[12], const float o[3], const float nd[3], const float* bounds) {
     using rtm::f3;
+    using namespace rtfast;
     const f3 O = rtm::mk(o[0], o[1], o[2]), N = rtm::mk(nd[0], nd[1], nd[2]), v0 = rtm::mk(rec[0], rec[1], rec[2]);
     const f3 e1 = rtm::mk(rec[3], rec[4], rec[5]), e2 = rtm::mk(rec[6], rec[7], rec[8]);
     auto glm = [&](f3 a, f3 b, float* det, float* u, float* v, float* uv) {  // (e1, e2) = (a, b)
@@ -39,11 +43,42 @@ extern "C" int rt_twin_check_host(const float rec[12], const float o[3], const f
     float d, u, v, uv, d2, u2, v2, uv2;
     glm(e1, e2, &d, &u, &v, &uv);
     glm(e2, e1, &d2, &u2, &v2, &uv2);
-    const f3 dist = rtm::sub(O, v0);
-    const float dn = (fabsf(dist.x) + fabsf(dist.y)) + fabsf(dist.z);
-    float kd, ke;
-    rt_twin_bounds(rec, &kd, &ke);
-    return (rtfast::twin_rejected(d, u, v, uv, dn, kd, ke) ? 1 : 0) | (ok(d2, u2, v2, uv2) ? 2 : 0) | (ok(d, u, v, uv) ? 4 : 0);
+    const int glm_bits = (ok(d2, u2, v2, uv2) ? 2 : 0) | (ok(d, u, v, uv) ? 4 : 0);
+    if (!bounds) {
+        const f3 dist = rtm::sub(O, v0);
+        const float dn = (fabsf(dist.x) + fabsf(dist.y)) + fabsf(dist.z);
+        float kd, ke;
+        rt_twin_bounds(rec, &kd, &ke);
+        return (twin_rejected(d, u, v, uv, dn, kd, ke) ? 1 : 0) | glm_bits;
+    }
+    const float dn = bounds[2], m = bounds[1] * dn + 0x1p-90f, m2 = 2.001f * m;
+    const float kdd = bounds[0] + 0x1p-90f, kdd1 = kdd * (1.0f + 0x1p-20f);
+    const bool scalar = twin_rejected_pre(d, u, v, uv, dn, m, m2, kdd, kdd1);
+    // quad_test's sequence, this triangle beside a degenerate one in the other half
+    bool same = true;
+    for (int half = 0; half < 2; half++) {
+        auto two = [&](float x) { return half ? f2{0.0f, x} : f2{x, 0.0f}; };
+        const f2 D = two(d);
+        const TwinFold<f2> F = twin_fold<f2>(D, two(u), two(v), two(uv), f2{copysignf(1.0f, D.x), copysignf(1.0f, D.y)});
+        const TwinLimits<f2> L = twin_limits<f2>(F.ad, F.suv, m, m2, kdd);
+        const bool packed = half ? twin_decide(F.ad.y, F.su.y, F.sv.y, dn, m, kdd1, L.top.y, L.lim_v.y, L.lim_uv.y, L.suv_lo.y)
+                                 : twin_decide(F.ad.x, F.su.x, F.sv.x, dn, m, kdd1, L.top.x, L.lim_v.x, L.lim_uv.x, L.suv_lo.x);
+        same = same && packed == scalar;
+        const bool okp = half ? tri_ok_folded(F.ad.y, F.su.y, F.sv.y, F.suv.y) : tri_ok_folded(F.ad.x, F.su.x, F.sv.x, F.suv.x);
+        same = same && okp == ok(d, u, v, uv);
+    }
+    return (scalar ? 1 : 0) | glm_bits | (same ? 0 : 8);
+}
+extern "C" int rt_twin_check_host(const float rec[12], const float o[3], const float nd[3]) {
+    return twin_check(rec, o, nd, nullptr);
+}
+extern "C" int rt_twin_check_bounds_host(const float rec[12], const float o[3], const float nd[3], const float bounds[3]) {
+    return twin_check(rec, o, nd, bounds);
+}
+// twin_visit (rt_fast.h) on the host: out = (DN, M, M2).
+extern "C" void rt_twin_visit_host(const float o[3], const float lo[3], const float hi[3], float ke, float out[3]) {
+    const rtfast::TwinVisit V = rtfast::twin_visit(rtm::mk(o[0], o[1], o[2]), rtm::mk(lo[0], lo[1], lo[2]), rtm::mk(hi[0], hi[1], hi[2]), ke);
+    out[0] = V.dn, out[1] = V.m, out[2] = V.m2;
 }
 
 // choose_variant (rt_variant.h) for tests/test_variant_cpu.py: in = {tune, stats, lane_cost, refill, has_tree, screens,

@@ -59,9 +59,9 @@ namespace {
 // The twins of big leaf [first, first + count) (mirror.h quads / units): units in leaf order, each a
 // triangle and (when the leaf holds one) its twin -- same v0, e1 and e2 swapped, bit for bit; a quad
 // packs two units.  Appends the leaf's quads and units; returns false (nothing appended) for a leaf
-// whose positions do not fit 16 bits.
+// whose positions do not fit 16 bits.  `leaf` receives the leaf's twin record (mirror.h pairs).
 bool build_twins(const float* tris, uint32_t first, uint32_t count, std::vector<float>& quads,
-                 std::vector<float>& units, uint32_t* nq, uint32_t* nu) {
+                 std::vector<float>& units, uint32_t* nq, uint32_t* nu, float leaf[20]) {
     if (count >= 0xffffu) return false;
     auto key = [&](uint32_t i, bool swapped) {
         const float* r = &tris[(size_t)(first + i) * 12];
@@ -123,6 +123,28 @@ bool build_twins(const float* tris, uint32_t first, uint32_t count, std::vector<
     }
     *nq = (uint32_t)((un.size() + 1) / 2);
     *nu = (uint32_t)un.size();
+    // the leaf's twin record: bounds that hold for every unit, so the kernel forms them once per leaf visit
+    float KD = 0.0f, KE = 0.0f, lo[3], hi[3];
+    for (size_t u = 0; u < un.size(); u++) {
+        const float* r = &tris[(size_t)(first + un[u].first) * 12];
+        for (int k = 0; k < 3; k++) {
+            lo[k] = u ? std::min(lo[k], r[k]) : r[k];
+            hi[k] = u ? std::max(hi[k], r[k]) : r[k];
+        }
+        if (un[u].second == none) continue;
+        float kd, ke;
+        rt_twin_bounds(r, &kd, &ke);
+        KD = std::max(KD, kd), KE = std::max(KE, ke);
+    }
+    auto up = [](double x) {  // the float at or above x
+        const float f = (float)x;
+        return (double)f < x ? std::nextafter(f, INFINITY) : f;
+    };
+    std::fill(leaf, leaf + 20, 0.0f);
+    leaf[0] = KD, leaf[1] = KE;
+    leaf[2] = up((double)KD + std::ldexp(1.0, -90));
+    leaf[3] = up((double)leaf[2] * (1.0 + std::ldexp(1.0, -20)));
+    for (int k = 0; k < 3; k++) leaf[4 + k] = lo[k], leaf[8 + k] = hi[k];
     return true;
 }
 }  // namespace
@@ -228,6 +250,20 @@ void rt_build_mirror(const GPUBVHNode* nodes, size_t node_count, const uint32_t*
             std::memcpy(&lead[11], &pf, 4);
             continue;
         }
+        // the twins; the leaf's second / third record say where its quads / units are, and the leaf's twin record
+        // goes in front of its screen record and pairs (mirror.h)
+        const uint32_t qb = (uint32_t)(out->quads.size() / 28), ub = (uint32_t)(out->units.size() / 16);
+        uint32_t nq = 0, nu = 0;
+        float twin_rec[20];
+        if (twins_ok && build_twins(out->tris.data(), nd.first_index, nd.prim_count, out->quads, out->units, &nq, &nu, twin_rec)) {
+            float* second = &out->tris[((size_t)nd.first_index + 1) * 12];
+            float* third = &out->tris[((size_t)nd.first_index + 2) * 12];
+            std::memcpy(&second[10], &qb, 4);
+            std::memcpy(&second[11], &nq, 4);
+            std::memcpy(&third[10], &ub, 4);
+            std::memcpy(&third[11], &nu, 4);
+            out->pairs.insert(out->pairs.end(), twin_rec, twin_rec + 20);
+        }
         // a screen record right before the pairs when the leaf has one (pf = 3, rt_fast.h screen_leaf)
         float scr[20];
         rt_build_options so;
@@ -248,17 +284,6 @@ void rt_build_mirror(const GPUBVHNode* nodes, size_t node_count, const uint32_t*
             put_pair(q, &out->tris[((size_t)nd.first_index + j) * 12],
                      j + 1 < nd.prim_count ? &out->tris[((size_t)nd.first_index + j + 1) * 12] : nullptr);
             out->pairs.insert(out->pairs.end(), q, q + 20);
-        }
-        // the twins; the leaf's second / third record say where its quads / units are (mirror.h)
-        const uint32_t qb = (uint32_t)(out->quads.size() / 28), ub = (uint32_t)(out->units.size() / 16);
-        uint32_t nq = 0, nu = 0;
-        if (twins_ok && build_twins(out->tris.data(), nd.first_index, nd.prim_count, out->quads, out->units, &nq, &nu)) {
-            float* second = &out->tris[((size_t)nd.first_index + 1) * 12];
-            float* third = &out->tris[((size_t)nd.first_index + 2) * 12];
-            std::memcpy(&second[10], &qb, 4);
-            std::memcpy(&second[11], &nq, 4);
-            std::memcpy(&third[10], &ub, 4);
-            std::memcpy(&third[11], &nu, 4);
         }
     }
     // every root's K3.x: the leaf-tree triangle count, the stride of their field-major device copy

@@ -14,7 +14,11 @@
 //           leaf's first tris record holds po = its first pair, pf = 1 (0 for other leaves), or
 //           pf = 3 when a screen record (leaftree.h rt_build_leaf_screen: the cull record of the
 //           leaf's core and the positions of its few big "outlier" triangles) sits in the 80-B slot
-//           just before the pairs, at po - 1 (rt_fast.h screen_leaf);
+//           just before the pairs, at po - 1 (rt_fast.h screen_leaf).  A leaf with twin records (below) has its
+//           TWIN RECORD in the 80-B slot before those, at po - 1 - (pf == 3): (KD, KE, KDD, KDD1), (lo.xyz, 0),
+//           (hi.xyz, 0), zeros -- KD / KE the largest kd / ke of the leaf's units that have a twin, KDD >=
+//           KD + 2^-90 and KDD1 >= KDD (1 + 2^-20) rounded up from double, [lo, hi] the box of the units' v0: what
+//           the twin test needs once per leaf visit instead of once per unit (rt_fast.h twin_visit);
 //  * quads / units  for the same leaves, their triangles by TWINS.  The reference adds every loaded
 //           face twice (Scene.cpp:103-127: the indexed face and AddTriangle's flat copy), and the two
 //           records share v0 with e1 and e2 swapped -- the same triangle, wound the other way -- so a

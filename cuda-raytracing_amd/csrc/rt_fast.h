@@ -300,6 +300,10 @@ __device__ __forceinline__ bool tri_ok(float det, float u, float v, float uv) {
     const float suv = __uint_as_float(__float_as_uint(uv) ^ sgn);
     return adet > eps && !(su < 0.0f || su > adet) && !(sv < 0.0f || suv > adet);
 }
+// ... from |det| and the sign-folded values (twin_fold).
+RT_HD bool tri_ok_folded(float adet, float su, float sv, float suv) {
+    return adet > 1.1920928955078125e-07f && !(su < 0.0f || su > adet) && !(sv < 0.0f || suv > adet);
+}
 
 // glm::intersectRayTriangle + BVHRayHit's accept test (`!(t >= best || t < 0)`) for one
 // candidate; returns whether it would be accepted against threshold `best`, and reports a
@@ -365,7 +369,6 @@ __device__ __forceinline__ Pair ld_pair(const float4* base, uint32_t p) {
 // perp = cross(dist, e1), v = dot(nd, perp)).
 struct PairEval {
     f2 det, u, v, uv, qx, qy, qz;  // q = perp
-    f2 dn;                         // |o - v0|_1 (computed; the twin test's bound, twin_rejected)
 };
 __device__ __forceinline__ PairEval pair_eval(f3 o, f3 nd, const Pair& P) {
     const f2 ndx = nd.x, ndy = nd.y, ndz = nd.z;
@@ -381,7 +384,6 @@ __device__ __forceinline__ PairEval pair_eval(f3 o, f3 nd, const Pair& P) {
     E.qz = dx * P.e1y - P.e1x * dy;
     E.v = (ndx * E.qx + ndy * E.qy) + ndz * E.qz;
     E.uv = E.u + E.v;
-    E.dn = f2{(fabsf(dx.x) + fabsf(dy.x)) + fabsf(dz.x), (fabsf(dx.y) + fabsf(dy.y)) + fabsf(dz.y)};
     return E;
 }
 
@@ -437,19 +439,87 @@ constexpr uint32_t NO_POS = 0xffffffffu;
 // fails `|det'| > eps && 0 <= su' <= |det'| && 0 <= sv' && suv' <= |det'|` if any bound already does.
 // Every threshold is widened by 2^-20 (> the rounding of these few operations) and by 2^-90 (underflow);
 // NaN, infinities and huge values are never decided here.
+//
+// The test is MONOTONE in its bounds: it answers true only where a condition fails by more than kdd >= kd +
+// 2^-90, kdd1 >= kdd (1 + 2^-20), m >= ke dn + 2^-90, m2 >= 2.001 m, or guard_dn >= dn puts the values in
+// range, and every one of them enters on the side that makes `true` harder (float sums and products of
+// non-negative values are monotone).  So larger values -- a leaf's largest kd and ke, a bound of |o - v0|_1
+// over the leaf (twin_visit) -- give a weaker, still sufficient test; a twin it no longer decides is tested
+// itself.  The arithmetic is written once for a float and for the two halves of a packed pair (V = f2:
+// v_pk_mul_f32 / v_pk_add_f32, per half exactly the scalar operation), the comparisons once per half.
+template <class V>
+struct TwinFold {
+    V ad, su, sv, suv;  // |det| and test_triangle's sign-folded u, v, u + v
+};
+// s = copysign(1, det): a product with +-1 is exact, so these are |det| and the values with det's sign bit
+// flipped in, as tri_ok forms them (a NaN may differ in sign: no comparison sees that)
+template <class V>
+RT_HD TwinFold<V> twin_fold(V det, V u, V v, V uv, V s) {
+    return TwinFold<V>{det * s, u * s, v * s, uv * s};
+}
+template <class V>
+struct TwinLimits {
+    V top, lim_v, lim_uv, suv_lo;
+};
+// a + b per half: a packed sum would keep a per-lane b in a register pair for the whole leaf visit
+RT_HD float add_each(float a, float b) { return a + b; }
+RT_HD f2 add_each(f2 a, float b) { return f2{a.x + b, a.y + b}; }
+template <class V>
+RT_HD TwinLimits<V> twin_limits(V ad, V suv, float m, float m2, V kdd) {
+    const V up = 1.0f + 0x1p-20f, down = 1.0f - 0x1p-20f;
+    const V t0 = ad + kdd;
+    return TwinLimits<V>{t0 * up, add_each(t0, m) * up, add_each(t0, m2) * up, suv * down};
+}
+// One predicate without short-circuit evaluation: |det'| <= eps, or det' has det's sign reversed and su' < 0
+// or sv' < 0 or su' > |det'| or suv' > |det'|.
+RT_HD bool twin_decide(float ad, float su, float sv, float guard_dn, float m, float kdd1, float top, float lim_v,
+                       float lim_uv, float suv_lo) {
+    const bool in_range = ad + fabsf(su) + fabsf(sv) + guard_dn < 0x1p100f;
+    const bool out = (sv < -m) | (su < -m) | (sv > lim_v) | (suv_lo > lim_uv);
+    return in_range & ((top <= 1.1920928955078125e-07f) | ((ad > kdd1) & out));
+}
+RT_HD bool twin_rejected_pre(float det, float u, float v, float uv, float guard_dn, float m, float m2, float kdd,
+                             float kdd1) {
+    const TwinFold<float> F = twin_fold<float>(det, u, v, uv, copysignf(1.0f, det));
+    const TwinLimits<float> L = twin_limits<float>(F.ad, F.suv, m, m2, kdd);
+    return twin_decide(F.ad, F.su, F.sv, guard_dn, m, kdd1, L.top, L.lim_v, L.lim_uv, L.suv_lo);
+}
+// The test from one triangle's own bounds (mirror.cpp rt_twin_bounds).
 RT_HD bool twin_rejected(float det, float u, float v, float uv, float dn, float kd, float ke) {
-    const bool neg = signbit(det);  // the sign fold of test_triangle (negation is exact)
-    const float ad = fabsf(det);
-    const float su = neg ? -u : u, sv = neg ? -v : v, suv = neg ? -uv : uv;
-    if (!(ad + fabsf(su) + fabsf(sv) + dn < 0x1p100f)) return false;
     const float m = ke * dn + 0x1p-90f;
     const float kdd = kd + 0x1p-90f;
-    const float top = (ad + kdd) * (1.0f + 0x1p-20f);
-    if (top <= 1.1920928955078125e-07f) return true;  // |det'| <= eps
-    if (!(ad > kdd * (1.0f + 0x1p-20f))) return false;  // det' may have either sign
-    if (sv < -m || su < -m) return true;                // su' < 0 or sv' < 0
-    if (sv > (ad + kdd + m) * (1.0f + 0x1p-20f)) return true;  // su' > |det'|
-    return suv * (1.0f - 0x1p-20f) > (ad + kdd + 2.001f * m) * (1.0f + 0x1p-20f);  // suv' > |det'|
+    return twin_rejected_pre(det, u, v, uv, dn, m, 2.001f * m, kdd, kdd * (1.0f + 0x1p-20f));
+}
+
+// The bounds of one ray's visit to a big leaf, from the leaf's twin record (mirror.h: KE, and the box [lo, hi]
+// of its units' v0).  dn >= every unit's computed |o - v0|_1: v0_a lies in [lo_a, hi_a], rounding is monotone,
+// so fl(o_a - v0_a) lies between fl(o_a - hi_a) and fl(o_a - lo_a) and its magnitude is at most the larger of
+// theirs; the three are then summed in the units' own order, again monotone.  (The factor 1 + 2^-20 is slack.)
+struct TwinVisit {
+    float dn, m, m2;
+};
+RT_HD float twin_visit_dn(f3 o, f3 lo, f3 hi) {
+    const float ax = fmaxf(fabsf(o.x - lo.x), fabsf(o.x - hi.x));
+    const float ay = fmaxf(fabsf(o.y - lo.y), fabsf(o.y - hi.y));
+    const float az = fmaxf(fabsf(o.z - lo.z), fabsf(o.z - hi.z));
+    return ((ax + ay) + az) * (1.0f + 0x1p-20f);
+}
+RT_HD TwinVisit twin_visit_from(float dn, float ke) {
+    TwinVisit V;
+    V.dn = dn;
+    V.m = ke * dn + 0x1p-90f;
+    V.m2 = 2.001f * V.m;
+    return V;
+}
+RT_HD TwinVisit twin_visit(f3 o, f3 lo, f3 hi, float ke) { return twin_visit_from(twin_visit_dn(o, lo, hi), ke); }
+// A leaf's twin record and this ray's bounds from it.
+struct TwinLeaf {
+    float ke, kdd, kdd1;
+    f3 lo, hi;
+};
+__device__ __forceinline__ TwinLeaf ld_twin_leaf(ConstF4 rec) {
+    const f4v k = rec[0], lo = rec[1], hi = rec[2];
+    return TwinLeaf{k.y, k.z, k.w, rtm::mk(lo.x, lo.y, lo.z), rtm::mk(hi.x, hi.y, hi.z)};
 }
 
 // A candidate under the sequential loop's rule in (t, position) order (h.best is the entry distance
@@ -484,15 +554,19 @@ __device__ __forceinline__ void tri_offer(f3 o, f3 nd, f3 v0, f3 e1, f3 e2, uint
 }
 
 // Quads (mirror.h): 7 float4 -- the pair layout (x5), the twin bounds (kd_a, kd_b, ke_a, ke_b; kd < 0:
-// no twin), and (pos_a | twin_a << 16, pos_b | twin_b << 16, twin face a, twin face b), read only on a
-// hit or a twin test.  One quad for one ray (the shared-leaf loop: scalar loads).
+// no twin; the test itself runs on the leaf's bounds K and the visit's B), and (pos_a | twin_a << 16,
+// pos_b | twin_b << 16, twin face a, twin face b), read only on a hit or a twin test.  One quad for one ray
+// (the shared-leaf loop: scalar loads).
 template <bool TIMING, class C>
-__device__ __forceinline__ void quad_test(f3 o, f3 nd, const Pair& P, f4v bnd, ConstF4 q6, Hit& h, uint32_t& bpos,
-                                          bool& nan, C& c) {
+__device__ __forceinline__ void quad_test(f3 o, f3 nd, const Pair& P, f4v bnd, const TwinLeaf& K, const TwinVisit& B,
+                                          ConstF4 q6, Hit& h, uint32_t& bpos, bool& nan, C& c) {
     const PairEval E = pair_eval(o, nd, P);
-    const bool oka = tri_ok(E.det.x, E.u.x, E.v.x, E.uv.x), okb = tri_ok(E.det.y, E.u.y, E.v.y, E.uv.y);
-    const bool twa = bnd.x >= 0.0f && !twin_rejected(E.det.x, E.u.x, E.v.x, E.uv.x, E.dn.x, bnd.x, bnd.z);
-    const bool twb = bnd.y >= 0.0f && !twin_rejected(E.det.y, E.u.y, E.v.y, E.uv.y, E.dn.y, bnd.y, bnd.w);
+    const f2 s = f2{copysignf(1.0f, E.det.x), copysignf(1.0f, E.det.y)};
+    const TwinFold<f2> F = twin_fold<f2>(E.det, E.u, E.v, E.uv, s);
+    const bool oka = tri_ok_folded(F.ad.x, F.su.x, F.sv.x, F.suv.x), okb = tri_ok_folded(F.ad.y, F.su.y, F.sv.y, F.suv.y);
+    const TwinLimits<f2> L = twin_limits<f2>(F.ad, F.suv, B.m, B.m2, K.kdd);
+    const bool twa = (bnd.x >= 0.0f) & !twin_decide(F.ad.x, F.su.x, F.sv.x, B.dn, B.m, K.kdd1, L.top.x, L.lim_v.x, L.lim_uv.x, L.suv_lo.x);
+    const bool twb = (bnd.y >= 0.0f) & !twin_decide(F.ad.y, F.su.y, F.sv.y, B.dn, B.m, K.kdd1, L.top.y, L.lim_v.y, L.lim_uv.y, L.suv_lo.y);
     if (TIMING) {  // timing frames: the production kernel's own big-leaf work (RT_STAT_BIG_TESTS, ...)
         c.big_tests += 2;
         c.tw_test += (uint32_t)twa + (uint32_t)twb;
@@ -501,16 +575,14 @@ __device__ __forceinline__ void quad_test(f3 o, f3 nd, const Pair& P, f4v bnd, C
     if (oka || okb || twa || twb) {  // rare: a hit, or a twin too close to call
         const f4v W = *q6;
         const uint32_t wa = __float_as_uint(W.x), wb = __float_as_uint(W.y);
-        if (oka) {
-            float inv;
-            const float t = pair_t(P, E, 0, &inv);
-            offer(t, wa & 0xffffu, P.fa, E.u.x * inv, E.v.x * inv, h, bpos, nan);
-        }
-        if (okb) {
-            float inv;
-            const float t = pair_t(P, E, 1, &inv);
-            offer(t, wb & 0xffffu, P.fb, E.u.y * inv, E.v.y * inv, h, bpos, nan);
-        }
+        // the triangles are evaluated again, as the twins are: the same operations in the same order give the packed
+        // halves' values bit for bit, and nothing of the pair's evaluation stays in registers for this path
+        if (oka)
+            tri_offer(o, nd, rtm::mk(P.v0x.x, P.v0y.x, P.v0z.x), rtm::mk(P.e1x.x, P.e1y.x, P.e1z.x),
+                      rtm::mk(P.e2x.x, P.e2y.x, P.e2z.x), wa & 0xffffu, P.fa, h, bpos, nan);
+        if (okb)
+            tri_offer(o, nd, rtm::mk(P.v0x.y, P.v0y.y, P.v0z.y), rtm::mk(P.e1x.y, P.e1y.y, P.e1z.y),
+                      rtm::mk(P.e2x.y, P.e2y.y, P.e2z.y), wb & 0xffffu, P.fb, h, bpos, nan);
         if (twa)
             tri_offer(o, nd, rtm::mk(P.v0x.x, P.v0y.x, P.v0z.x), rtm::mk(P.e2x.x, P.e2y.x, P.e2z.x),
                       rtm::mk(P.e1x.x, P.e1y.x, P.e1z.x), wa >> 16, __float_as_uint(W.z), h, bpos, nan);
@@ -522,10 +594,13 @@ __device__ __forceinline__ void quad_test(f3 o, f3 nd, const Pair& P, f4v bnd, C
 
 // Units (mirror.h): 4 float4 -- a triangle record (v0, e1, e2, face) with (twin face, pos | twin << 16)
 // in its last two words, and (kd, ke, 0, 0); kd < 0: no twin.  One unit for one ray (cooperative
-// rounds: a lane per unit).
+// rounds: a lane per unit).  Of the unit's own bounds only kd's sign is read; the test runs on the leaf's (K, in
+// SGPRs) and on the unit's own |o - v0|_1: at seven waves a SIMD the cooperative rounds have no register left to carry a ray's bound
+// of it through their loops (one more live value there spills the traversal stack's registers into the small-step
+// loop); the shared-leaf loop has.
 template <bool TIMING, class C>
-__device__ __forceinline__ void unit_test(f3 o, f3 nd, float4 A, float4 B, float4 Cc, float4 D, Hit& h, uint32_t& bpos,
-                                          bool& nan, C& c) {
+__device__ __forceinline__ void unit_test(f3 o, f3 nd, float4 A, float4 B, float4 Cc, float kd, const TwinLeaf& K,
+                                          Hit& h, uint32_t& bpos, bool& nan, C& c) {
     const f3 v0 = rtm::mk(A.x, A.y, A.z), e1 = rtm::mk(A.w, B.x, B.y), e2 = rtm::mk(B.z, B.w, Cc.x);
     const f3 p = rtm::cross(nd, e2);
     const float det = rtm::dot(e1, p);
@@ -540,8 +615,9 @@ __device__ __forceinline__ void unit_test(f3 o, f3 nd, float4 A, float4 B, float
         offer(rtm::dot(e2, perp) * inv_det, w & 0xffffu, __float_as_uint(Cc.y), u * inv_det, v * inv_det, h, bpos, nan);
     }
     const float dn = (fabsf(dist.x) + fabsf(dist.y)) + fabsf(dist.z);
-    const bool tw = D.x >= 0.0f && !twin_rejected(det, u, v, uv, dn, D.x, D.y);
-    if (TIMING) c.big_tests++, c.tw_test += (uint32_t)tw, c.tw_dec += (uint32_t)(D.x >= 0.0f && !tw);
+    const TwinVisit V = twin_visit_from(dn, K.ke);
+    const bool tw = (kd >= 0.0f) & !twin_rejected_pre(det, u, v, uv, V.dn, V.m, V.m2, K.kdd, K.kdd1);
+    if (TIMING) c.big_tests++, c.tw_test += (uint32_t)tw, c.tw_dec += (uint32_t)(kd >= 0.0f && !tw);
     if (tw) tri_offer(o, nd, v0, e2, e1, w >> 16, __float_as_uint(Cc.z), h, bpos, nan);
 }
 
@@ -633,8 +709,8 @@ __device__ __forceinline__ void coop_leaf(const float4* tris, const float4* pair
 // its (t, position)-first candidate (offer); the wave's (t, position) arg-min is the sequential loop's
 // result.  A NaN distance, or a NaN entry distance, runs the sequential loop.
 template <bool TIMING, class C>
-__device__ __forceinline__ void coop_units(const float4* tris, const float4* un, uint32_t nu, unsigned long long big,
-                                           uint32_t f0, uint32_t c0, const Ray& R, Hit& h, C& c) {
+__device__ __forceinline__ void coop_units(const float4* tris, const float4* un, uint32_t nu, const TwinLeaf& K,
+                                           unsigned long long big, uint32_t f0, uint32_t c0, const Ray& R, Hit& h, C& c) {
     const uint32_t lane = threadIdx.x & 63u;
     unsigned long long m = big;
     while (m) {
@@ -647,7 +723,7 @@ __device__ __forceinline__ void coop_units(const float4* tris, const float4* un,
         uint32_t bpos = NO_POS;
         bool nan = !(L.best == L.best);
         for (uint32_t q = lane; q < nu; q += 64u)
-            unit_test<TIMING>(rox, nd, un[4 * q], un[4 * q + 1], un[4 * q + 2], un[4 * q + 3], L, bpos, nan, c);
+            unit_test<TIMING>(rox, nd, un[4 * q], un[4 * q + 1], un[4 * q + 2], un[4 * q + 3].x, K, L, bpos, nan, c);
         if (TIMING && lane == 0) c.big_iters += (nu + 63u) / 64u;
         if (__ballot(nan)) {
             if ((int)lane == r) leaf_sequential(tris, f0, c0, R.o, R.nd, h);
@@ -1267,17 +1343,20 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
         // the first record of a big leaf says where its pairs are, the second where its twin quads are (mirror.h)
         const f4v lead = ((ConstF4)(tris + 3 * (size_t)f0))[2];
         const uint32_t k = (uint32_t)__popcll(big);
-        if (!STATS && (MODE & BIG_MASK) < BIG_SCALAR && (LEAN || quads) && (__float_as_uint(lead.w) & 1u)) {
+        if (!STATS && (MODE & BIG_MASK) < BIG_SCALAR && (LEAN || (quads && pairs)) && (__float_as_uint(lead.w) & 1u)) {
             // the second record: the leaf's first quad and quad count, the third: first unit and count
             const f4v l2 = ((ConstF4)(tris + 3 * (size_t)f0 + 3))[2];
             const f4v l3 = ((ConstF4)(tris + 3 * (size_t)f0 + 6))[2];
             const uint32_t nq = __float_as_uint(l2.w), nu = __float_as_uint(l3.w);
+            // the leaf's twin record, in front of its screen record (kind 3) and pairs
+            const uint32_t pk = __float_as_uint(lead.w);
+            const TwinLeaf K = ld_twin_leaf((ConstF4)(pairs + 5 * (size_t)(__float_as_uint(lead.z) - 1u - ((pk >> 1) & 1u))));
             // cost model (VALU instructions): cooperative ~ k * (70 * chunks + 70) over the units,
             // shared ~ 95 * nq over the quads for all waiting lanes at once
             // RT_TUNE bits 21-23: the cooperative side's weight in quarters (0 = 4, the default)
             const uint32_t cw = (tune >> 21) & 7u;
             if (nu && (tune & 1u) == 0 && k * (70u * ((nu + 63u) / 64u) + 70u) * (cw ? cw : 4u) < 4u * 95u * nq) {
-                coop_units<(MODE & TIMING_BIT) != 0>(tris, units + 4 * (size_t)__float_as_uint(l3.z), nu, big, f0, c0, R, h, c);
+                coop_units<(MODE & TIMING_BIT) != 0>(tris, units + 4 * (size_t)__float_as_uint(l3.z), nu, K, big, f0, c0, R, h, c);
                 if (MODE & TIMING_BIT) c.r_coop++, c.coop_rays += k;
                 return waiting;
             }
@@ -1286,11 +1365,12 @@ __device__ __forceinline__ bool big_round(const float4* tris, const float4* pair
                 const Hit h0 = h;
                 uint32_t bpos = NO_POS;
                 bool nan = !(h.best == h.best);
+                const TwinVisit B = twin_visit(R.o, K.lo, K.hi, K.ke);  // this lane's ray, once per leaf visit
                 ConstF4 qs = (ConstF4)(quads + 7 * (size_t)__float_as_uint(l2.z));
                 for (uint32_t q = 0; q < nq; q++, qs += 7) {
                     const Pair P = make_pair(qs[0], qs[1], qs[2], qs[3], qs[4]);
                     const f4v bnd = qs[5];
-                    if (waiting) quad_test<(MODE & TIMING_BIT) != 0>(R.o, R.nd, P, bnd, qs + 6, h, bpos, nan, c);
+                    if (waiting) quad_test<(MODE & TIMING_BIT) != 0>(R.o, R.nd, P, bnd, K, B, qs + 6, h, bpos, nan, c);
                 }
                 if (MODE & TIMING_BIT) c.big_iters += nq;
                 if (waiting && nan) {  // the sequential loop from the entry distance (never taken for finite scenes)

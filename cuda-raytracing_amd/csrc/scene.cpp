@@ -730,6 +730,23 @@ int rt_scene_mirror_twins(rt_scene* s, float* quads, size_t* quad_count, float* 
     if (units) std::memcpy(units, m.units.data(), m.units.size() * 4);
     return 0;
 }
+int rt_scene_mirror_leaf_twin(rt_scene* s, uint32_t first, float rec[12]) {
+    MirrorHost m;
+    if (host_mirror(s, &m) != 0) return -1;
+    uint32_t po = 0, pf = 0, nq = 0;
+    if ((size_t)first + 2 < m.tris.size() / 12) {
+        std::memcpy(&po, &m.tris[(size_t)first * 12 + 10], 4);
+        std::memcpy(&pf, &m.tris[(size_t)first * 12 + 11], 4);
+        std::memcpy(&nq, &m.tris[((size_t)first + 1) * 12 + 11], 4);
+    }
+    const uint32_t back = 1u + (pf == 3u ? 1u : 0u);
+    if (!m.twins || (pf != 1u && pf != 3u) || nq == 0 || po < back || (size_t)po * 20 > m.pairs.size()) {
+        rt_internal_set_error("rt_scene_mirror_leaf_twin: not the first record of a big leaf with twin records");
+        return -1;
+    }
+    std::memcpy(rec, &m.pairs[(size_t)(po - back) * 20], 12 * 4);
+    return 0;
+}
 int rt_scene_mirror_face_leaf(rt_scene* s, uint32_t* leaf, size_t* count) {
     MirrorHost m;
     if (host_mirror(s, &m) != 0) return -1;

@@ -1278,6 +1278,13 @@ int rt_cluster_cull_host(const float origin[3], const float nd[3], float best, c
    the twin of triangle record `rec` (v0, e2, e1) is proven rejected from rec's own glm values for the
    ray (origin, nd), bit 1 the twin passes glm's predicate, bit 2 rec does.  For tests. */
 int rt_twin_check_host(const float rec[12], const float origin[3], const float nd[3]);
+/* The same with the bounds the render kernel uses, formed once per leaf visit (rt_fast.h twin_rejected_pre,
+   twin_visit): bounds = (KD, KE, DN) stands for the triangle's own (kd, ke, |origin - v0|_1).  Bits 0-2 as
+   above, bit 0 by the hoisted form; bit 3: the packed evaluation of the shared-leaf loop (both halves) and the
+   scalar one disagree.  For tests. */
+int rt_twin_check_bounds_host(const float rec[12], const float origin[3], const float nd[3], const float bounds[3]);
+/* twin_visit on the host: out = (DN, M, M2) for a ray origin, the box [lo, hi] of a leaf's v0 and its KE. */
+void rt_twin_visit_host(const float origin[3], const float lo[3], const float hi[3], float ke, float out[3]);
 /* The render kernel variant rt_render chooses for a frame (csrc/rt_variant.h choose_variant), on the host and
    without a GPU: in = {tune, stats, lane_cost, refill, has_tree, screens, arrays_complete, depth, want_entry},
    out = {family, mode, stack, needs_plugin, use_entry}.  rt_family_has_mode_host: 1 when the translation unit
@@ -1291,6 +1298,9 @@ int rt_scene_mirror_nodes(rt_scene* scene, GPUBVHNode* nodes, size_t* count);
 /* The big leaves' twin records (mirror.h quads: 28 floats each, units: 16 floats each), built on the
    host: counts first, then the arrays when the pointers are not NULL.  0 or -1. */
 int rt_scene_mirror_twins(rt_scene* scene, float* quads, size_t* quad_count, float* units, size_t* unit_count);
+/* The twin record (mirror.h pairs: KD, KE, KDD, KDD1, lo.xyz, 0, hi.xyz, 0) of the big leaf whose first
+   leaf-ordered record is `first`, built on the host.  0, or -1 when that leaf has no twin records. */
+int rt_scene_mirror_leaf_twin(rt_scene* scene, uint32_t first, float rec[12]);
 /* Scenes with big leaves: the leaf of every face (mirror.h face_leaf: the private node index, 0xffffffff
    in no leaf, 0xfffffffe in two), which the deferred leaves' guard reads (rt_fast.h).  *count receives
    the face count (0 for scenes without big leaves); leaf (may be NULL) the table.  0 or -1. */
