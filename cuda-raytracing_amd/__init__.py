@@ -107,6 +107,23 @@ class OcclusionParams(ctypes.Structure):
                 ("flags", ctypes.c_uint32), ("waves_per_simd", ctypes.c_int32)]
 
 
+class Point(ctypes.Structure):
+    """rt_point (rt_abi.h): one row of a float32 [N, 4] point tensor."""
+    _fields_ = [("position", ctypes.c_float * 3), ("radius", ctypes.c_float)]
+
+
+class Nearest(ctypes.Structure):
+    """rt_nearest (rt_abi.h): one row of a float32 [N, 8] record tensor (nearest_fields gives typed views)."""
+    _fields_ = [("distance", ctypes.c_float), ("kind", ctypes.c_uint32), ("id", ctypes.c_uint32),
+                ("material", ctypes.c_uint32), ("point", ctypes.c_float * 3), ("region", ctypes.c_uint32)]
+
+
+class ClosestParams(ctypes.Structure):
+    """rt_closest_params (rt_abi.h)."""
+    _fields_ = [("points", ctypes.c_void_p), ("count", ctypes.c_int64), ("nearest", ctypes.c_void_p),
+                ("flags", ctypes.c_uint32), ("waves_per_simd", ctypes.c_int32)]
+
+
 class AoParams(ctypes.Structure):
     """rt_ao_params (rt_abi.h)."""
     _fields_ = [("hits", ctypes.c_void_p), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
@@ -219,6 +236,7 @@ REPROJECT_DEFAULT = -1  # RT_REPROJECT_DEFAULT: in a filter parameter of rt_repr
 REPROJECT_DEFAULTS = {"max_history": 32, "sigma_plane": 0.03, "normal_min": 0.9}
 assert ctypes.sizeof(ReprojectParams) == 224 and ctypes.sizeof(GPUCamera) == 60
 assert ctypes.sizeof(RadianceParams) == 48
+assert ctypes.sizeof(Point) == 16 and ctypes.sizeof(Nearest) == 32 and ctypes.sizeof(ClosestParams) == 32
 # the defaults rt_denoise_variance substitutes (csrc/denoise_variance.hip; profiles/variance_quality.txt)
 DENOISE_VARIANCE_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_plane": 0.03, "sigma_lum": 4.0, "min_history": 4.0}
 assert ctypes.sizeof(MomentsParams) == 64 and ctypes.sizeof(DenoiseVarianceParams) == 136
@@ -236,6 +254,9 @@ SIGNATURES = {
     "rt_render": (_I, [ctypes.POINTER(RenderParams), _P, _P]),
     "rt_trace_rays": (_I, [ctypes.POINTER(TraceParams), _P, _P]),
     "rt_occluded": (_I, [ctypes.POINTER(OcclusionParams), _P, _P]),
+    "rt_closest_point": (_I, [ctypes.POINTER(ClosestParams), _P, _P]),
+    "rt_closest_point_host": (_I, [_P, _P, ctypes.c_int64, _P]),
+    "rt_closest_bound_host": (_F, [_P, _P, _P]),
     "rt_ao_scratch_bytes": (_SZ, [_I, _I, _I]),
     "rt_ao": (_I, [ctypes.POINTER(AoParams), _P, _P]),
     "rt_radiance": (_I, [ctypes.POINTER(RadianceParams), _P, _P]),
@@ -754,6 +775,72 @@ def occluded(scene, rays, out=None, stream=None, waves_per_simd=0):
     p.waves_per_simd = int(waves_per_simd)
     _check(lib().rt_occluded(ctypes.byref(p), _scene_ptr(scene), _stream_ptr(stream)), "rt_occluded")
     return out
+
+
+NEAREST_MISS, NEAREST_SPHERE, NEAREST_FACE = 0, 1, 2  # rt_nearest.kind
+
+
+def closest_points(scene, points, out=None, waves_per_simd=0, stream=None):
+    """rt_closest_point: the nearest point of the scene's surface to every row of a float32 CUDA tensor [N, 4]
+    (rt_point rows: position, search radius -- inf for none), as a float32 [N, 8] tensor of rt_nearest rows (`out`, or
+    a new one; nearest_fields gives typed views): distance, kind, id, material, the point, the triangle's region.  A
+    point with nothing within its radius gets a miss: its radius and zeros.  Exact and unsigned (rt_abi.h).
+    Stream-ordered on `stream` (default: torch's current stream)."""
+    assert points.dtype == torch.float32 and points.is_cuda and points.is_contiguous() and points.dim() == 2
+    assert points.shape[1] == 4
+    n = points.shape[0]
+    if out is None:
+        with _allocating_on(stream):
+            out = torch.empty((n, 8), dtype=torch.float32, device=points.device)
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.dim() == 2
+    assert out.shape[1] == 8 and out.shape[0] >= n
+    if n == 0:  # rt_closest_point returns at once for count 0; an empty tensor has no address to pass
+        return out
+    p = ClosestParams()
+    p.points, p.count, p.nearest = points.data_ptr(), n, out.data_ptr()
+    p.waves_per_simd = int(waves_per_simd)
+    _check(lib().rt_closest_point(ctypes.byref(p), _scene_ptr(scene), _stream_ptr(stream)), "rt_closest_point")
+    return out
+
+
+def nearest_fields(nearest):
+    """Typed views of a [N, 8] record tensor (torch or numpy): distance, kind / id / material / region (int32),
+    point [N, 3]."""
+    ints = nearest.view(torch.int32) if isinstance(nearest, torch.Tensor) else nearest.view(np.int32)
+    return {"distance": nearest[:, 0], "kind": ints[:, 1], "id": ints[:, 2], "material": ints[:, 3],
+            "point": nearest[:, 4:7], "region": ints[:, 7]}
+
+
+def closest_points_host(scene, points):
+    """rt_closest_point_host: closest_points' records by brute force on the host (a built or uploaded Scene, a
+    float32 numpy array [N, 4]) as a float32 numpy array [N, 8].  No BVH and no device: for checking."""
+    pts = np.ascontiguousarray(points, dtype=np.float32)
+    assert pts.ndim == 2 and pts.shape[1] == 4
+    out = np.zeros((pts.shape[0], 8), dtype=np.float32)
+    _check(lib().rt_closest_point_host(scene.handle, pts.ctypes.data, pts.shape[0], out.ctypes.data), "rt_closest_point_host")
+    return out
+
+
+def closest_bound_host(p, lo, hi):
+    """closest.h box_bound on the host (rt_closest_bound_host): the kernel's lower bound on the computed squared
+    distance from p to any face with its vertices in the box [lo, hi]; -1 = no bound."""
+    return float(lib().rt_closest_bound_host(_f3(p), _f3(lo), _f3(hi)))
+
+
+def distance_grid(scene, lo, hi, shape, radius=float("inf"), stream=None, waves_per_simd=0):
+    """The unsigned distance from the centre of every cell of a regular grid to the scene's surface: `shape` =
+    (nz, ny, nx) cells over the box [lo, hi] (x, y, z), as a float32 device tensor [nz, ny, nx].  A cell with nothing
+    within `radius` holds `radius`.  Tensor code over closest_points."""
+    nz, ny, nx = (int(s) for s in shape)
+    with _allocating_on(stream):
+        axes = []
+        for n, a, b in ((nx, lo[0], hi[0]), (ny, lo[1], hi[1]), (nz, lo[2], hi[2])):
+            i = torch.arange(n, dtype=torch.float32, device="cuda")
+            axes.append(float(a) + (i + 0.5) * ((float(b) - float(a)) / n))
+        z, y, x = torch.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+        pts = torch.stack([x, y, z, torch.full_like(x, float(radius))], dim=-1).reshape(-1, 4).contiguous()
+    rec = closest_points(scene, pts, stream=stream, waves_per_simd=waves_per_simd)
+    return rec[:, 0].reshape(nz, ny, nx).clone()
 
 
 def radiance(scene, rays, rng, bounces=REFERENCE_BOUNCES, samples=1, out=None, stream=None, waves_per_simd=0):
@@ -1745,6 +1832,14 @@ class RayTracer:
             with _allocating_on(stream):
                 hits = trace_camera(self.scene, self.width, self.height, stream=stream)
         return ambient_occlusion(self.scene, hits, self.width, self.height, radius, **kw)
+
+    def closest_points(self, points, **kw):
+        """The nearest surface point of every row of a [N, 4] point tensor (module-level closest_points(); **kw are
+        its out, waves_per_simd, stream).  Uploads the scene like process() and works before any frame is rendered;
+        the frame index, the surfaces and the RNG states are left alone."""
+        self.scene.set_viewport(self.width, self.height)
+        self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
+        return closest_points(self.scene, points, **kw)
 
     def panorama(self, width, height, origin=None, samples=None, bounces=None, seed=None, stream=None):
         """A width x height equirectangular panorama of the scene seen from `origin` (default: the camera's position),

@@ -1,6 +1,6 @@
-// rt_batch_calls.hip -- the entry points of the ray-batch calls (rt_abi.h): rt_trace_rays, rt_occluded, rt_ao,
-// rt_radiance and rt_sample_pixels.  Each makes the checks that need no device first, then the scene's and the
-// buffers', then launches its kernel (rt_query.hip, rt_occlude.hip, rt_radiance.hip, rt_adaptive.hip: rt_render.h)
+// rt_batch_calls.hip -- the entry points of the batch calls (rt_abi.h): rt_trace_rays, rt_occluded, rt_closest_point,
+// rt_ao, rt_radiance and rt_sample_pixels.  Each makes the checks that need no device first, then the scene's and the
+// buffers', then launches its kernel (rt_query.hip, rt_occlude.hip, rt_closest.hip, rt_radiance.hip, rt_adaptive.hip: rt_render.h)
 // in the variant a production frame of the scene runs at RT_TUNE 0.  Stream-ordered: no synchronisation, no
 // allocation.  No kernel lives here.
 #include <hip/hip_runtime.h>
@@ -138,6 +138,45 @@ extern "C" int rt_occluded(const rt_occlusion_params* p, const GPUScene* scene, 
     a.occluded = p->occluded;
     const int w = batch_waves(p->waves_per_simd, v, true);
     return check(launch_occlusion(v.stack, v.mode, w, a, (hipStream_t)stream), "occlusion_kernel launch");
+}
+
+// The occupancy of rt_closest_point when the call asks for none, measured (profiles/closest_timing.txt, 2^20 points):
+// 7 waves per SIMD, a tie with 6 and 5 inside the spread on every batch -- config 2's scene, points uniform in the box,
+// radius inf: 7.23 vs 7.24 / 7.25 ms at 6 / 5; on the surface 5.72 vs 5.71 / 5.69; far outside 2.17 vs 2.23 / 2.25;
+// config 4's scene (leaf tree) 35.8 vs 35.6 / 35.9, 75.2 vs 73.9 / 73.7 and 9.44 vs 9.50 / 9.66 ms.  The tie is no
+// surprise: the kernel takes 59 registers and spills nothing (profiles/closest_resources.txt), so the three builds are
+// one code and each fits 8 waves; 7 stays the default, as for the ray calls on scenes without leaf trees.
+static int closest_waves(int asked) { return asked ? asked : 7; }
+
+// Closest-point queries: the closest-point kernel (rt_closest.hip) on the scene half of a ray-batch launch.
+extern "C" int rt_closest_point(const rt_closest_params* p, const GPUScene* scene, void* stream) {
+    const char* const who = "rt_closest_point";
+    if (!p) return refuse(who, "null params");
+    if (!scene) return refuse(who, "null scene");
+    if (!p->nearest) return refuse(who, "null nearest");
+    if (!p->points) return refuse(who, "null points");
+    if (p->flags != 0) return refuse(who, "flags must be 0");
+    if (waves_refused(who, p->waves_per_simd)) return 1;
+    if (p->count < 0) return refuse(who, "negative count");
+    if (p->count > (int64_t)1 << 31) return refuse(who, "more than 2^31 points in one call");
+    if (misaligned(who, "points and nearest", 16, {p->points, p->nearest})) return 1;
+    if (p->count == 0) return 0;
+
+    QueryArgs q;
+    Variant v;
+    if (query_scene(who, scene, &q, &v) != 0) return 1;
+    const size_t n = (size_t)p->count;
+    if (too_small(who, "points", p->points, n * sizeof(rt_point)) || too_small(who, "nearest", p->nearest, n * sizeof(rt_nearest)))
+        return 1;
+    // a lane reads its point when it starts: a record written over a later point would change it
+    if (overlap(p->nearest, n * sizeof(rt_nearest), p->points, n * sizeof(rt_point))) return refuse(who, "nearest overlaps points");
+    ClosestArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.points = p->points, a.nearest = p->nearest, a.count = p->count;
+    a.spheres = q.spheres, a.sphere_count = q.sphere_count, a.scene_fast = q.scene_fast;
+    a.faces = q.faces, a.nodes = q.nodes, a.tris = q.tris;
+    a.tree = q.ltris ? q.tree : nullptr, a.ltris = q.ltris;
+    return check(launch_closest(v.stack, closest_waves(p->waves_per_simd), a, (hipStream_t)stream), "closest_kernel launch");
 }
 
 // The fused AO kernel keeps its samples in registers: no scratch.

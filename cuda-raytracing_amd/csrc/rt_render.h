@@ -113,6 +113,23 @@ struct SampleArgs {
 static_assert(offsetof(SampleArgs, r) == 0, "the kernel-argument segment starts with the RenderArgs");
 hipError_t launch_sample_pixels(int stack, int mode, int waves_per_simd, const SampleArgs& a, hipStream_t s);
 
+// The closest-point kernel (rt_closest.hip, rt_closest_point): one point per lane over the mirror's private nodes,
+// leaf-ordered records and leaf trees, culling by distance to a box (closest.h).  No MODE: stack 30 / 40 / 64 and the
+// occupancy alone choose the build.
+struct ClosestArgs {
+    const rt_point* points;
+    rt_nearest* nearest;
+    long long count;
+    const GeometrySphere* spheres;
+    int sphere_count;
+    int scene_fast;  // every node bound inside the mirror's `fast` range: closest.h box_bound's premise on the boxes
+    const GPUFace* faces;  // the winner's material
+    const GPUBVHNode* nodes;  // the mirror's private node array
+    const FlatTri* tris;
+    const float4 *tree, *ltris;  // null: the scene has no leaf tree
+};
+hipError_t launch_closest(int stack, int waves_per_simd, const ClosestArgs& a, hipStream_t s);
+
 // In librt_hip_exp.so beside its families:
 // The lone-pixel kernel (rt_lone.hip): one wave per slot of `lone_slots`, through the treelets.
 hipError_t launch_lone(const RenderArgs& a, const int32_t* lone_slots, int lone_count, const void* treelets, hipStream_t s);

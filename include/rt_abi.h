@@ -504,6 +504,89 @@ static_assert(sizeof(rt_radiance_params) == 48 && offsetof(rt_radiance_params, r
 int rt_radiance(const rt_radiance_params* params, const GPUScene* scene, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Closest-point queries: "which point of the scene's surface is nearest to p, and how far is it?" (distance
+ * fields, snapping and picking without a direction, proximity effects, mesh-to-mesh distance, a conservative step
+ * for sphere tracing).  The third query beside closest-hit (rt_trace_rays) and any-hit (rt_occluded).
+ *
+ * THE ANSWER IS DEFINED WITHOUT REFERENCE TO ANY TRAVERSAL, so it is exact, bit for bit.  With r2 = radius * radius,
+ * the record of point p is the lexicographic minimum of (d2, kind, id) over all spheres (kind 1, id = the sphere's
+ * index) and all faces (kind 2, id = the face's index) whose computed d2 satisfies d2 <= r2; a NaN d2 is never
+ * accepted.  Then distance = sqrt(d2) (IEEE), point = q, material = the primitive's, region as below.  If nothing
+ * is accepted the record is a miss: distance = radius as passed (its bits) and every other word 0.  The id rule
+ * matters on every loaded mesh: each loaded face is in the scene twice, wound both ways, the twin always ties, and
+ * the lower face index wins.
+ *
+ * The arithmetic is fp32 without contraction: + - * /, sqrt and comparisons only, in exactly this order.
+ * dot(u, v) = (u.x * v.x + u.y * v.y) + u.z * v.z; vector operations are per component.
+ *
+ * Sphere (c, rad):
+ *   v = p - c;  len = sqrt(dot(v, v));  s = len - rad;  dist = s < 0 ? -s : s;  d2 = dist * dist;
+ *   q = len > 0 ? c + v * (rad / len) : c + (rad, 0, 0);  region = 0.
+ *
+ * Face f:  a = vertices[f.v0].position, ab = vertices[f.v1].position - a, ac = vertices[f.v2].position - a (v1 and
+ * v2 read by name: GPUFace above).
+ *   ap = p - a;  d1 = dot(ab, ap);  d2_ = dot(ac, ap);  aa = dot(ab, ab);  bb = dot(ab, ac);  cc = dot(ac, ac);
+ *   d3 = d1 - aa;  d4 = d2_ - bb;  d5 = d1 - bb;  d6 = d2_ - cc;  ratio(n, d) = d > 0 ? n / d : 0.
+ *   The first rule that holds:
+ *   1. d1 <= 0 && d2_ <= 0:                                        v = 0, w = 0, region 1
+ *   2. d3 >= 0 && d4 <= d3:                                        v = 1, w = 0, region 2
+ *   3. vc = d1 * d4 - d3 * d2_;  vc <= 0 && d1 >= 0 && d3 <= 0:    v = ratio(d1, d1 - d3), w = 0, region 4
+ *   4. d6 >= 0 && d5 <= d6:                                        v = 0, w = 1, region 3
+ *   5. vb = d5 * d2_ - d1 * d6;  vb <= 0 && d2_ >= 0 && d6 <= 0:   v = 0, w = ratio(d2_, d2_ - d6), region 5
+ *   6. va = d3 * d6 - d5 * d4;  va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0:
+ *                                           w = ratio(d4 - d3, (d4 - d3) + (d5 - d6)), v = 1 - w, region 6
+ *   7. otherwise: den = (va + vb) + vc;  v = ratio(vb, den);  w = ratio(vc, den);  then, as selects (a NaN stays a
+ *      NaN):  v = v < 0 ? 0 : v;  v = v > 1 ? 1 : v;  w = w < 0 ? 0 : w;  w = w > 1 - v ? 1 - v : w;  region 0
+ *   q = (a + ab * v) + ac * w;  e = p - q;  d2 = dot(e, e).
+ * Regions: 0 the interior, 1 / 2 / 3 the vertices v0 / v1 / v2, 4 / 5 / 6 the edges v0v1 / v0v2 / v1v2.  A
+ * degenerate triangle answers as its vertex or segment (ratio gives 0 for 0 / 0).
+ *
+ * The distance is UNSIGNED.  Signed distance is out of scope: with every loaded face present in both windings, the
+ * side of the winning triangle says nothing.
+ * ------------------------------------------------------------------------------------- */
+typedef struct rt_point {
+    float position[3];
+    float radius;  /* search radius: only primitives with d2 <= radius * radius answer; +inf = no limit; NaN = a miss */
+} rt_point; /* 16 B */
+
+typedef struct rt_nearest {
+    float distance;  /* sqrt(d2); on a miss the radius as passed */
+    uint32_t kind;   /* 0 miss, 1 sphere, 2 face */
+    uint32_t id;     /* sphere index / face index */
+    uint32_t material;
+    float point[3];  /* q, the nearest point of the surface */
+    uint32_t region; /* faces: 0 interior, 1-3 vertex, 4-6 edge; spheres: 0 */
+} rt_nearest; /* 32 B */
+
+typedef struct rt_closest_params {
+    const rt_point* points; /* DEVICE, count records, 16-byte aligned, not NULL */
+    int64_t count;          /* 0 returns at once; at most 2^31 */
+    rt_nearest* nearest;    /* DEVICE, 16-byte aligned, one record per point; records at and past count untouched */
+    uint32_t flags;         /* must be 0 */
+    int32_t waves_per_simd; /* occupancy build of the kernel: 5 / 6 / 7, or 0 = the measured default (7; the three
+                               tie: profiles/closest_timing.txt) */
+} rt_closest_params;        /* 32 B */
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_point) == 16 && offsetof(rt_point, position) == 0 && offsetof(rt_point, radius) == 12, "rt_point");
+static_assert(sizeof(rt_nearest) == 32 && offsetof(rt_nearest, distance) == 0 && offsetof(rt_nearest, kind) == 4 &&
+              offsetof(rt_nearest, id) == 8 && offsetof(rt_nearest, material) == 12 && offsetof(rt_nearest, point) == 16 &&
+              offsetof(rt_nearest, region) == 28, "rt_nearest");
+static_assert(sizeof(rt_closest_params) == 32 && offsetof(rt_closest_params, points) == 0 &&
+              offsetof(rt_closest_params, count) == 8 && offsetof(rt_closest_params, nearest) == 16 &&
+              offsetof(rt_closest_params, flags) == 24 && offsetof(rt_closest_params, waves_per_simd) == 28,
+              "rt_closest_params");
+#endif
+
+/* Nearest points of a batch on `stream` (a hipStream_t, NULL = null stream): stream-ordered, no synchronisation,
+ * no allocation, one kernel launch.  The scene rules are rt_trace_rays': uploaded by rt_scene_upload, a GPUScene
+ * filled by another host is rejected.  The arguments that need no device are checked first, in rt_occluded's order
+ * (NULL params, scene, nearest or points; flags; waves_per_simd; count < 0 or > 2^31; alignment), then the scene
+ * and the buffer sizes; `nearest` may not overlap `points`.  Every message begins with "rt_closest_point: ".
+ * Returns 0 or an error code with rt_last_error(). */
+int rt_closest_point(const rt_closest_params* params, const GPUScene* scene, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Denoising: a viewable image from one low-sample frame and the first-hit records of its camera
  * (render -> rt_trace_rays in camera mode -> rt_denoise).  An edge-avoiding a-trous wavelet filter on
  * the frame divided by the first hit's albedo, guided by normal, position and distance; the albedo
@@ -1305,6 +1388,14 @@ int rt_scene_mirror_leaf_twin(rt_scene* scene, uint32_t first, float rec[12]);
    in no leaf, 0xfffffffe in two), which the deferred leaves' guard reads (rt_fast.h).  *count receives
    the face count (0 for scenes without big leaves); leaf (may be NULL) the table.  0 or -1. */
 int rt_scene_mirror_face_leaf(rt_scene* scene, uint32_t* leaf, size_t* count);
+/* rt_closest_point's answer by brute force on the host, over the scene's host arrays (no BVH, no device): every
+   sphere and every face for every point, by the kernel's own source (csrc/closest.h).  The oracle of the GPU tests
+   on scenes too large for an interpreter; itself pinned to a numpy restatement of the rules (tests/closest_ref.py).
+   0, or -1 with rt_last_error(). */
+int rt_closest_point_host(rt_scene* scene, const rt_point* points, int64_t count, rt_nearest* out);
+/* closest.h box_bound on the host, for tests: the lower bound of the computed d2 of every face whose vertices lie in
+   the box [lo, hi] (-1: no bound), which the kernel's cull compares with the best so far. */
+float rt_closest_bound_host(const float p[3], const float lo[3], const float hi[3]);
 
 /* Test hook: the private mirror built on the host from raw reference arrays (the foreign-scene path,
    rt_render on a GPUScene not uploaded by rt_scene_upload): words 10-11 of every leaf-ordered record --
