@@ -124,6 +124,13 @@ class ClosestParams(ctypes.Structure):
                 ("flags", ctypes.c_uint32), ("waves_per_simd", ctypes.c_int32)]
 
 
+class HitsParams(ctypes.Structure):
+    """rt_hits_params (rt_abi.h)."""
+    _fields_ = [("rays", ctypes.c_void_p), ("count", ctypes.c_int64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("hits", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("max_hits", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("waves_per_simd", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
 class AoParams(ctypes.Structure):
     """rt_ao_params (rt_abi.h)."""
     _fields_ = [("hits", ctypes.c_void_p), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
@@ -257,6 +264,8 @@ SIGNATURES = {
     "rt_closest_point": (_I, [ctypes.POINTER(ClosestParams), _P, _P]),
     "rt_closest_point_host": (_I, [_P, _P, ctypes.c_int64, _P]),
     "rt_closest_bound_host": (_F, [_P, _P, _P]),
+    "rt_trace_hits": (_I, [ctypes.POINTER(HitsParams), _P, _P]),
+    "rt_hit_list_host": (_I, [_I, _F, _I, ctypes.c_int64, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int64)]),
     "rt_ao_scratch_bytes": (_SZ, [_I, _I, _I]),
     "rt_ao": (_I, [ctypes.POINTER(AoParams), _P, _P]),
     "rt_radiance": (_I, [ctypes.POINTER(RadianceParams), _P, _P]),
@@ -827,20 +836,128 @@ def closest_bound_host(p, lo, hi):
     return float(lib().rt_closest_bound_host(_f3(p), _f3(lo), _f3(hi)))
 
 
+def _grid_axes(lo, hi, shape):
+    """The cell centres of a (nz, ny, nx) grid over the box [lo, hi] as device tensors (z, y, x)."""
+    axes = []
+    for n, a, b in ((shape[0], lo[2], hi[2]), (shape[1], lo[1], hi[1]), (shape[2], lo[0], hi[0])):
+        i = torch.arange(n, dtype=torch.float32, device="cuda")
+        axes.append(float(a) + (i + 0.5) * ((float(b) - float(a)) / n))
+    return axes
+
+
 def distance_grid(scene, lo, hi, shape, radius=float("inf"), stream=None, waves_per_simd=0):
     """The unsigned distance from the centre of every cell of a regular grid to the scene's surface: `shape` =
     (nz, ny, nx) cells over the box [lo, hi] (x, y, z), as a float32 device tensor [nz, ny, nx].  A cell with nothing
     within `radius` holds `radius`.  Tensor code over closest_points."""
     nz, ny, nx = (int(s) for s in shape)
     with _allocating_on(stream):
-        axes = []
-        for n, a, b in ((nx, lo[0], hi[0]), (ny, lo[1], hi[1]), (nz, lo[2], hi[2])):
-            i = torch.arange(n, dtype=torch.float32, device="cuda")
-            axes.append(float(a) + (i + 0.5) * ((float(b) - float(a)) / n))
-        z, y, x = torch.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+        z, y, x = torch.meshgrid(*_grid_axes(lo, hi, (nz, ny, nx)), indexing="ij")
         pts = torch.stack([x, y, z, torch.full_like(x, float(radius))], dim=-1).reshape(-1, 4).contiguous()
     rec = closest_points(scene, pts, stream=stream, waves_per_simd=waves_per_simd)
     return rec[:, 0].reshape(nz, ny, nx).clone()
+
+
+HITS_MAX = 16  # RT_HITS_MAX
+RT_HITS_CULL_BACK, RT_HITS_CULL_FRONT, RT_HITS_COUNT_ALL = 1, 2, 4  # rt_hits_params.flags
+
+
+def _trace_hits(scene, rays, count, width, height, max_hits, flags, hits, counts, stream, waves_per_simd):
+    k = int(max_hits)
+    device = rays.device if rays is not None else "cuda"
+    with _allocating_on(stream):
+        if hits is None:
+            hits = torch.empty((count, k, 12), dtype=torch.float32, device=device)
+        if counts is None:
+            counts = torch.empty((count,), dtype=torch.int32, device=device)
+    assert hits.dtype == torch.float32 and hits.is_cuda and hits.is_contiguous() and hits.dim() == 3
+    assert hits.shape[1] == k and hits.shape[2] == 12 and hits.shape[0] >= count
+    if counts is not False:
+        assert counts.dtype == torch.int32 and counts.is_cuda and counts.is_contiguous() and counts.dim() == 1
+        assert counts.shape[0] >= count
+    if count == 0:  # rt_trace_hits returns at once for count 0; an empty tensor has no address to pass
+        return hits, (None if counts is False else counts)
+    p = HitsParams()
+    p.rays = rays.data_ptr() if rays is not None else None
+    p.count, p.width, p.height = count, width, height
+    p.hits = hits.data_ptr()
+    p.counts = None if counts is False else counts.data_ptr()
+    p.max_hits, p.flags, p.waves_per_simd = k, int(flags), int(waves_per_simd)
+    _check(lib().rt_trace_hits(ctypes.byref(p), _scene_ptr(scene), _stream_ptr(stream)), "rt_trace_hits")
+    return hits, (None if counts is False else counts)
+
+
+def trace_hits(scene, rays, max_hits, flags=0, hits=None, counts=None, stream=None, waves_per_simd=0):
+    """rt_trace_hits: the first `max_hits` (1..16) hits of every ray of a float32 CUDA tensor [N, 8] (rt_ray rows), in
+    order of distance, as (hits, counts): a float32 [N, K, 12] tensor of rt_hit rows -- row k of a ray its k-th hit, the
+    rows past the last a miss record (t = tmax, zeros) -- and an int32 [N] tensor of list lengths.  flags:
+    RT_HITS_CULL_BACK / RT_HITS_CULL_FRONT keep one winding's triangles (on a loaded mesh: one record per crossing),
+    RT_HITS_COUNT_ALL makes counts the number of all hits below tmax (it may exceed K).  `hits` / `counts`: tensors to
+    fill in place (counts=False: none kept, None is returned for it).  Exact, as trace_rays (rt_abi.h); stream-ordered
+    on `stream` (default: torch's current stream)."""
+    assert _is_rays(rays)
+    return _trace_hits(scene, rays, rays.shape[0], 0, 0, max_hits, flags, hits, counts, stream, waves_per_simd)
+
+
+def trace_hits_camera(scene, width, height, max_hits, flags=0, hits=None, counts=None, stream=None, waves_per_simd=0):
+    """rt_trace_hits in camera mode: trace_camera's rays (the pixel centres of the uploaded scene's camera), ray i =
+    pixel (i % width, i // width); (hits [H*W, K, 12], counts [H*W])."""
+    return _trace_hits(scene, None, int(width) * int(height), int(width), int(height), max_hits, flags, hits, counts, stream,
+                       waves_per_simd)
+
+
+def hit_list_host(t, payload, max_hits, tmax, count_all=False):
+    """rt_hit_list_host: the kernel's list code (csrc/hit_list.h) on the host -- the pairs (t[j], payload[j]) offered in
+    order to an empty list of `max_hits` entries under `tmax`.  Returns (t float32 [n], payload uint32 [n], total)."""
+    t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1)
+    payload = np.ascontiguousarray(payload, dtype=np.uint32).reshape(-1)
+    assert t.shape == payload.shape
+    out_t, out_p = np.zeros(HITS_MAX, dtype=np.float32), np.zeros(HITS_MAX, dtype=np.uint32)
+    total = ctypes.c_int64(0)
+    n = lib().rt_hit_list_host(int(max_hits), float(tmax), 1 if count_all else 0, t.shape[0], t.ctypes.data, payload.ctypes.data,
+                               out_t.ctypes.data, out_p.ctypes.data, ctypes.byref(total))
+    if n < 0:
+        raise RTError("rt_hit_list_host failed: " + lib().rt_last_error().decode(errors="replace"))
+    return out_t[:n].copy(), out_p[:n].copy(), int(total.value)
+
+
+# contains(): three fixed unit directions in general position (no component 0, none parallel to a box face or diagonal)
+CONTAINS_DIRECTIONS = ((0.36, 0.48, 0.8), (-0.6, 0.64, -0.48), (0.8, -0.36, 0.48))
+
+
+def contains(scene, points, flags=RT_HITS_CULL_BACK, stream=None, waves_per_simd=0):
+    """Whether each row of a float32 CUDA tensor [N, 3] lies inside a closed body of the scene, as a bool tensor [N]:
+    the parity of the surface crossings along a ray to infinity, counted under one winding (rt_trace_hits with
+    RT_HITS_COUNT_ALL | `flags`, so that a loaded mesh's twin faces count once), by majority over three fixed
+    directions.  Meaningful for closed surfaces; spheres count as they are crossed (one distance each)."""
+    assert points.dtype == torch.float32 and points.is_cuda and points.dim() == 2 and points.shape[1] == 3
+    n = points.shape[0]
+    with _allocating_on(stream):
+        votes = torch.zeros((n,), dtype=torch.int32, device=points.device)
+        rays = torch.zeros((n, 8), dtype=torch.float32, device=points.device)
+        rays[:, 0:3] = points
+        rays[:, 3] = RAY_TMAX
+        hits = torch.empty((n, 1, 12), dtype=torch.float32, device=points.device)
+    for d in CONTAINS_DIRECTIONS:
+        with _allocating_on(stream):
+            rays[:, 4:7] = torch.tensor(d, dtype=torch.float32, device=points.device)
+        _, counts = trace_hits(scene, rays, 1, flags=RT_HITS_COUNT_ALL | int(flags), hits=hits, stream=stream,
+                               waves_per_simd=waves_per_simd)
+        with _allocating_on(stream):
+            votes += counts & 1
+    with _allocating_on(stream):
+        return votes >= 2
+
+
+def signed_distance_grid(scene, lo, hi, shape, radius=float("inf"), flags=RT_HITS_CULL_BACK, stream=None, waves_per_simd=0):
+    """distance_grid with a sign: the same distances (bit for bit), negated at the cell centres `contains` finds inside."""
+    nz, ny, nx = (int(s) for s in shape)
+    dist = distance_grid(scene, lo, hi, shape, radius=radius, stream=stream, waves_per_simd=waves_per_simd)
+    with _allocating_on(stream):
+        z, y, x = torch.meshgrid(*_grid_axes(lo, hi, (nz, ny, nx)), indexing="ij")
+        pts = torch.stack([x, y, z], dim=-1).reshape(-1, 3).contiguous()
+    inside = contains(scene, pts, flags=flags, stream=stream).reshape(nz, ny, nx)
+    with _allocating_on(stream):
+        return torch.where(inside, -dist, dist)
 
 
 def radiance(scene, rays, rng, bounces=REFERENCE_BOUNCES, samples=1, out=None, stream=None, waves_per_simd=0):
@@ -1840,6 +1957,23 @@ class RayTracer:
         self.scene.set_viewport(self.width, self.height)
         self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
         return closest_points(self.scene, points, **kw)
+
+    def layers(self, max_hits, flags=0, stream=None, waves_per_simd=0):
+        """The first `max_hits` surfaces behind every pixel (trace_hits_camera: the pixel centres, no jitter) as device
+        tensors, rows bottom to top like the surface: depth [H, W, K] (t; inf past the last hit), prim (sphere or face
+        index, -1 past the last hit) and kind [H, W, K] int32, and count [H, W] int32 (the list length, or with
+        RT_HITS_COUNT_ALL in `flags` every hit below tmax).  Uploads the scene like process(); the frame index, the
+        surfaces and the RNG states are left alone."""
+        self.scene.set_viewport(self.width, self.height)
+        self.scene.upload(self.rng.data_ptr() if self.rng is not None else 0)
+        w, h, k = self.width, self.height, int(max_hits)
+        hits, counts = trace_hits_camera(self.scene, w, h, k, flags=flags, stream=stream, waves_per_simd=waves_per_simd)
+        with _allocating_on(stream):
+            f = hit_fields(hits.reshape(w * h * k, 12))
+            hit = f["kind"] != HIT_MISS
+            return {"depth": torch.where(hit, f["t"], torch.full_like(f["t"], float("inf"))).reshape(h, w, k),
+                    "prim": torch.where(hit, f["id"], torch.full_like(f["id"], -1)).reshape(h, w, k),
+                    "kind": f["kind"].reshape(h, w, k).clone(), "count": counts.reshape(h, w)}
 
     def panorama(self, width, height, origin=None, samples=None, bounces=None, seed=None, stream=None):
         """A width x height equirectangular panorama of the scene seen from `origin` (default: the camera's position),

@@ -40,7 +40,7 @@ HIP_CODEGEN_FLAGS = ["-mllvm", "-structurizecfg-skip-uniform-regions=1", "-mllvm
 HOST_SOURCES = ["scene.cpp", "objload.cpp", "mirror.cpp", "leaftree.cpp", "xorwow.cpp", "image.cpp", "shard.cpp", "closest_host.cpp"]
 # the render kernel families compile as separate translation units, in parallel (rt_render.h)
 HIP_SOURCES = ["rt_fast_prod.hip", "rt_fast_lean.hip", "rt_fast_timing.hip", "rt_fast_stats.hip", "rt_ref.hip", "rt_kernel.hip", "image.hip",
-               "bvh_build.hip", "comm.hip", "rt_query.hip", "rt_occlude.hip", "rt_radiance.hip", "rt_closest.hip", "denoise.hip", "denoise_variance.hip",
+               "bvh_build.hip", "comm.hip", "rt_query.hip", "rt_occlude.hip", "rt_radiance.hip", "rt_closest.hip", "rt_hits.hip", "denoise.hip", "denoise_variance.hip",
                "reproject.hip", "rt_adaptive.hip", "sample_plan.hip", "upsample.hip",
                # the host side behind the C-ABI, by concern (rt_host.h); rt_kernel.hip above is its base
                "rt_render.hip", "rt_batch_calls.hip", "rng_shard.hip", "entry_table.hip", "foreign.hip", "host_hooks.hip"]

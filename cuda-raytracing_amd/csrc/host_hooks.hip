@@ -1,5 +1,6 @@
 // host_hooks.hip -- device code's decisions evaluated on the host by the same source, for the tests: the twin test and
-// the leaf-tree cull predicate of rt_fast.h, the variant chooser of rt_variant.h and the family table of rt_render.h.
+// the leaf-tree cull predicate of rt_fast.h, the hit list of hit_list.h, the variant chooser of rt_variant.h and the
+// family table of rt_render.h.
 #include <hip/hip_runtime.h>
 
 #include "rt_abi.h"
@@ -10,7 +11,9 @@
 #include "rt_fast.h"
 #include "mirror.h"
 #include "rt_render.h"
+#include "hit_list.h"
 
+static_assert(RT_HITS_MAX == rth::MAX_HITS, "hit_list.h holds at most RT_HITS_MAX entries");
 static_assert(MIRROR_BIG_LEAF == (uint32_t)rtfast::BIG, "pair records exist for exactly the big leaves");
 
 // 1 when librt_hip_exp.so's render paths are registered (rt_render.h ExperimentalKernels).
@@ -100,6 +103,26 @@ extern "C" int rt_family_has_mode_host(int family, int mode) {
 #undef RT_FAMILY_CASE
     }
     return 0;
+}
+
+// rt_trace_hits' list (hit_list.h) on the host, for tests/test_hits_cpu.py: the offers in order, arrival breaking ties.
+extern "C" int rt_hit_list_host(int max_hits, float tmax, int count_all, int64_t n, const float* t, const uint32_t* payload,
+                                float* out_t, uint32_t* out_payload, int64_t* total) {
+    if (max_hits < 1 || max_hits > rth::MAX_HITS || n < 0 || (n > 0 && (!t || !payload)) || !out_t || !out_payload) {
+        rt_internal_set_error("rt_hit_list_host: max_hits outside 1..16, negative n or a null array");
+        return -1;
+    }
+    rth::List<rth::MAX_HITS> L;
+    rth::init(L, max_hits, tmax);
+    for (int64_t j = 0; j < n; j++) rth::offer(L, count_all != 0, t[j], payload[j]);
+    int held = 0;
+    for (int s = rth::MAX_HITS - max_hits; s < rth::MAX_HITS; s++) {
+        if (L.p[s] == rth::EMPTY) break;
+        out_t[held] = L.t[s], out_payload[held] = L.p[s];
+        held++;
+    }
+    if (total) *total = (int64_t)L.total;
+    return held;
 }
 
 // The leaf-tree cull predicate of the render kernel (rt_fast.h cluster_cull), for tests/test_leaf_tree.py.

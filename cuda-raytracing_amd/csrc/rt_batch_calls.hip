@@ -1,8 +1,8 @@
 // rt_batch_calls.hip -- the entry points of the batch calls (rt_abi.h): rt_trace_rays, rt_occluded, rt_closest_point,
-// rt_ao, rt_radiance and rt_sample_pixels.  Each makes the checks that need no device first, then the scene's and the
-// buffers', then launches its kernel (rt_query.hip, rt_occlude.hip, rt_closest.hip, rt_radiance.hip, rt_adaptive.hip: rt_render.h)
-// in the variant a production frame of the scene runs at RT_TUNE 0.  Stream-ordered: no synchronisation, no
-// allocation.  No kernel lives here.
+// rt_trace_hits, rt_ao, rt_radiance and rt_sample_pixels.  Each makes the checks that need no device first, then the
+// scene's and the buffers', then launches its kernel (rt_query.hip, rt_occlude.hip, rt_closest.hip, rt_hits.hip,
+// rt_radiance.hip, rt_adaptive.hip: rt_render.h) in the variant a production frame of the scene runs at RT_TUNE 0.
+// Stream-ordered: no synchronisation, no allocation.  No kernel lives here.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -177,6 +177,55 @@ extern "C" int rt_closest_point(const rt_closest_params* p, const GPUScene* scen
     a.faces = q.faces, a.nodes = q.nodes, a.tris = q.tris;
     a.tree = q.ltris ? q.tree : nullptr, a.ltris = q.ltris;
     return check(launch_closest(v.stack, closest_waves(p->waves_per_simd), a, (hipStream_t)stream), "closest_kernel launch");
+}
+
+// The occupancy of rt_trace_hits when the call asks for none, from the compiler's figures (profiles/hits_resources.txt):
+// the 4-slot list takes 71 registers and spills nothing, so its three builds are one code and run at 7 like the other
+// ray calls; the 8- and 16-slot lists spill least at 5 (0 and 38 vector registers, against 26 and 162 at 7).
+// tools/hits_timing.py measures the choice (profiles/hits_timing.txt).
+static int hits_waves(int asked, int max_hits) { return asked ? asked : max_hits <= 4 ? 7 : 5; }
+
+// Ordered hits: the hits kernel (rt_hits.hip) on the scene half of a ray-batch launch, the device-free checks in the
+// order the header states.
+extern "C" int rt_trace_hits(const rt_hits_params* p, const GPUScene* scene, void* stream) {
+    const char* const who = "rt_trace_hits";
+    if (!p) return refuse(who, "null params");
+    if (!scene) return refuse(who, "null scene");
+    if (!p->hits) return refuse(who, "null hits");
+    const uint32_t known = RT_HITS_CULL_BACK | RT_HITS_CULL_FRONT | RT_HITS_COUNT_ALL, both = RT_HITS_CULL_BACK | RT_HITS_CULL_FRONT;
+    if (p->flags & ~known) return refuse(who, "unknown flag bits");
+    if ((p->flags & both) == both) return refuse(who, "RT_HITS_CULL_BACK and RT_HITS_CULL_FRONT exclude each other");
+    if (p->reserved != 0) return refuse(who, "reserved must be 0");
+    if (waves_refused(who, p->waves_per_simd)) return 1;
+    if (p->max_hits < 1 || p->max_hits > RT_HITS_MAX) return refuse(who, "max_hits must be 1..16");
+    const bool camera = p->rays == nullptr;
+    if (camera && (p->width <= 0 || p->height <= 0)) return refuse(who, "camera mode needs width, height > 0");
+    const int64_t count = camera ? (int64_t)p->width * p->height : p->count;
+    if (count_refused(who, count) || misaligned(who, "rays and hits", 16, {p->rays, p->hits}) ||
+        misaligned(who, "counts", 4, {p->counts}))
+        return 1;
+    if (count == 0) return 0;
+
+    QueryArgs q;
+    Variant v;
+    if (query_scene(who, scene, &q, &v) != 0) return 1;
+    const size_t n = (size_t)count, hit_bytes = n * (size_t)p->max_hits * sizeof(rt_hit);
+    if (!camera && too_small(who, "rays", p->rays, n * sizeof(rt_ray))) return 1;
+    if (too_small(who, "hits", p->hits, hit_bytes)) return 1;
+    if (p->counts && too_small(who, "counts", p->counts, n * 4)) return 1;
+    // a lane reads its ray when it starts: a row or a count written over a later ray would change it
+    if (overlap(p->hits, hit_bytes, p->rays, n * sizeof(rt_ray))) return refuse(who, "hits overlaps rays");
+    if (overlap(p->counts, n * 4, p->rays, n * sizeof(rt_ray))) return refuse(who, "counts overlaps rays");
+    if (overlap(p->counts, n * 4, p->hits, hit_bytes)) return refuse(who, "counts overlaps hits");
+    HitsArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.rays = p->rays, a.hits = p->hits, a.counts = p->counts, a.count = count;
+    a.width = camera ? p->width : 1, a.height = camera ? p->height : 1, a.cam = q.cam;
+    a.max_hits = p->max_hits, a.flags = p->flags;
+    a.spheres = q.spheres, a.sphere_count = q.sphere_count, a.scene_fast = q.scene_fast;
+    a.faces = q.faces, a.vertices = q.vertices, a.nodes = q.nodes, a.tris = q.tris;
+    a.tree = q.ltris ? q.tree : nullptr, a.ltris = q.ltris;
+    return check(launch_hits(v.stack, hits_waves(p->waves_per_simd, p->max_hits), a, (hipStream_t)stream), "hits_kernel launch");
 }
 
 // The fused AO kernel keeps its samples in registers: no scratch.

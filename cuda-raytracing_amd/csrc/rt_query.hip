@@ -9,28 +9,6 @@
 namespace rtk {
 namespace {
 
-// Ray i of the launch: the caller's record as two 16-byte loads (adjacent lanes, adjacent records), or the
-// camera ray through the centre of pixel (i % width, i / width) in the operation order of render_fast_body's
-// sample start.  Called again after the traversal, so that only the index is carried across it.
-__device__ __forceinline__ void query_ray(const QueryArgs& q, long long i, rtm::f3& ro, rtm::f3& rd, float& tmax) {
-    if (q.rays) {
-        const float4* const r = reinterpret_cast<const float4*>(q.rays + i);
-        const float4 a = r[0], b = r[1];
-        ro = rtm::mk(a.x, a.y, a.z);
-        tmax = a.w;
-        rd = rtm::mk(b.x, b.y, b.z);
-    } else {
-        const int x = (int)(i % q.width), y = (int)(i / q.width);
-        const float uvx = ((float)x + 0.5f) / (float)q.width;
-        const float uvy = ((float)y + 0.5f) / (float)q.height;
-        const rtm::f3 co = ld3(q.cam.origin), ch = ld3(q.cam.horizontal), cv = ld3(q.cam.vertical),
-                      cl = ld3(q.cam.lower_left_corner);
-        ro = co;
-        rd = rtm::sub(rtm::add(rtm::add(cl, rtm::muls(ch, uvx)), rtm::muls(cv, uvy)), co);
-        tmax = 1e30f;
-    }
-}
-
 template <int STACK, int MODE>
 __device__ __forceinline__ void query_body(const QueryArgs& q, const rtfast::Stack<RT_BATCH_SL(STACK)>& stk,
                                            uint32_t* const scratch) {

@@ -130,6 +130,30 @@ struct ClosestArgs {
 };
 hipError_t launch_closest(int stack, int waves_per_simd, const ClosestArgs& a, hipStream_t s);
 
+// The ordered-hits kernel (rt_hits.hip, rt_trace_hits): one ray per lane, a per-lane walk of the mirror's private nodes
+// with the rt_fast.h pieces (make_ray, inner_step, pop), the first max_hits accepted distances kept in a register list
+// (hit_list.h).  rays, width, height and cam as QueryArgs (rt_batch.h query_ray).  No MODE: the list's capacity
+// (4 / 8 / 16 >= max_hits), stack 30 / 40 / 64 and the occupancy choose the build.
+struct HitsArgs {
+    const rt_ray* rays;  // null: camera mode
+    rt_hit* hits;        // count * max_hits records
+    uint32_t* counts;    // null: none kept
+    long long count;
+    int width, height;
+    GPUCamera cam;
+    int max_hits;
+    uint32_t flags;  // RT_HITS_*
+    const GeometrySphere* spheres;
+    int sphere_count;
+    int scene_fast;
+    const GPUFace* faces;
+    const GPUVertex* vertices;
+    const GPUBVHNode* nodes;  // the mirror's private node array
+    const FlatTri* tris;
+    const float4 *tree, *ltris;  // null: the scene has no leaf tree
+};
+hipError_t launch_hits(int stack, int waves_per_simd, const HitsArgs& a, hipStream_t s);
+
 // In librt_hip_exp.so beside its families:
 // The lone-pixel kernel (rt_lone.hip): one wave per slot of `lone_slots`, through the treelets.
 hipError_t launch_lone(const RenderArgs& a, const int32_t* lone_slots, int lone_count, const void* treelets, hipStream_t s);

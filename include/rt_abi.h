@@ -541,8 +541,8 @@ int rt_radiance(const rt_radiance_params* params, const GPUScene* scene, void* s
  * Regions: 0 the interior, 1 / 2 / 3 the vertices v0 / v1 / v2, 4 / 5 / 6 the edges v0v1 / v0v2 / v1v2.  A
  * degenerate triangle answers as its vertex or segment (ratio gives 0 for 0 / 0).
  *
- * The distance is UNSIGNED.  Signed distance is out of scope: with every loaded face present in both windings, the
- * side of the winning triangle says nothing.
+ * The distance is UNSIGNED.  Signed distance is out of scope here: with every loaded face present in both windings, the
+ * side of the winning triangle says nothing.  (The sign comes from counting crossings under one winding: rt_trace_hits.)
  * ------------------------------------------------------------------------------------- */
 typedef struct rt_point {
     float position[3];
@@ -585,6 +585,89 @@ static_assert(sizeof(rt_closest_params) == 32 && offsetof(rt_closest_params, poi
  * and the buffer sizes; `nearest` may not overlap `points`.  Every message begins with "rt_closest_point: ".
  * Returns 0 or an error code with rt_last_error(). */
 int rt_closest_point(const rt_closest_params* params, const GPUScene* scene, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Ordered hits: "what does this ray go through, in order?" (transparency and depth peeling, x-ray and thickness
+ * images, picking through a front surface, counting crossings to tell inside from outside).  The fourth query beside
+ * closest-hit (rt_trace_rays), any-hit (rt_occluded) and nearest-point (rt_closest_point).  A crossing count under
+ * one winding is also the sign rt_closest_point cannot give: see RT_HITS_CULL_BACK below.
+ *
+ * THE RULE.  rt_trace_hits is the reference's GetRayHit / BVHRayHit (main_raytracing.cu:33-109) with its single
+ * closest distance replaced by a list of K = max_hits.  For ray i:
+ *
+ *   nd = normalize(direction);  list = empty;  total = 0.
+ *   bound() = the K-th smallest accepted t once K are held, tmax before that; under RT_HITS_COUNT_ALL tmax throughout.
+ *   offer(t, kind, id):  if t is NaN, t < 0 or !(t < bound()): nothing.  Otherwise total += 1; the entry goes in
+ *     before the first entry whose t is strictly greater -- an equal t goes behind the ones already there, so arrival
+ *     order breaks ties, as the reference's strict < does -- and the list is cut to K.
+ *   Spheres k = 0 .. sphere_count - 1: where glm's sphere test hits, offer(dist, 1, k) -- one distance per sphere, as
+ *     in the reference.
+ *   Then BVHRayHit: right-first DFS, the slab test on the direction as given, exactly as rt_trace_rays runs it, its
+ *     clause `tmin < closest` reading `tmin < bound()` at the moment the reference would pop the node.  A leaf's
+ *     triangles go in leaf order; where glm's triangle test hits (on nd), offer(t, 2, face).
+ *
+ * Flags.  RT_HITS_CULL_BACK offers a triangle only when the test's det > 0, RT_HITS_CULL_FRONT only when det < 0
+ * (det = dot(v1 - v0, cross(nd, v2 - v0)) with v1 and v2 read by name: det > 0 when the ray runs against
+ * cross(v1 - v0, v2 - v0).  GPUFace's field order swaps the two, so for rt_scene_add_triangle(a, b, c) that is a ray
+ * running along cross(b - a, c - a): it meets the side on which a, b, c wind clockwise); both at once are refused.  Since |det| > epsilon for every triangle the test accepts, the sign is never
+ * in doubt.  Spheres are never culled.  On a loaded mesh, where every face is present in both windings (a twin has
+ * det' = -det), either cull flag leaves one record per crossing.  RT_HITS_COUNT_ALL: the bound stays tmax, so every
+ * hit in [0, tmax) of every node the walk visits is counted in `total` while the list keeps the first K.
+ *
+ * Output.  hits[i * max_hits + k] for k < the list's length is a full rt_hit: t, kind, id as offered, and the
+ * attributes rt_trace_rays computes for that primitive and t (same arithmetic, same normal flip).  Every remaining row
+ * of the ray is rt_trace_rays' miss record (t = tmax as passed, every other word 0), so buffers compare bytewise.
+ * counts[i] (counts may be NULL) is the list's length, at most K; under RT_HITS_COUNT_ALL it is `total`, which may
+ * exceed K.
+ *
+ * K = 1 AND THE NaN RULE.  With max_hits 1 and flags 0, row 0 equals rt_trace_rays' record bytewise for every ray
+ * whose reference traversal accepts no NaN distance -- every ray inside rt_occluded's gate, for one.  The one
+ * deliberate difference from the reference is that a NaN distance is never accepted (the reference lets it through,
+ * after which nothing more is accepted and the ray reports a miss).  A NaN tmax gives all misses, as it does there.
+ *
+ * NO PREFIX GUARANTEE.  The list for K is not promised to be a prefix of the list for K' > K, nor to hold "all
+ * geometric hits": the reference's fp32 box test culls against the bound, and with a direction shorter than 1 it
+ * culls early -- the precondition rt_trace_rays states and this call inherits.  With unit directions the lists of
+ * every scene tried were prefixes of one another; that is an observation, not a contract.
+ * ------------------------------------------------------------------------------------- */
+#define RT_HITS_MAX 16
+enum {
+    RT_HITS_CULL_BACK = 1,  /* offer a triangle only when det > 0 */
+    RT_HITS_CULL_FRONT = 2, /* ... only when det < 0 */
+    RT_HITS_COUNT_ALL = 4,  /* bound() = tmax throughout; counts[i] = total */
+};
+
+typedef struct rt_hits_params {
+    const rt_ray* rays;     /* DEVICE, count records, 16-byte aligned; NULL = camera mode: the pixel-centre rays exactly as
+                               rt_trace_rays forms them */
+    int64_t count;          /* rays (ignored in camera mode); 0 returns at once; at most 2^31 */
+    int32_t width, height;  /* camera mode only */
+    rt_hit* hits;           /* DEVICE, count * max_hits records, 16-byte aligned; rows at and past count * max_hits untouched */
+    uint32_t* counts;       /* DEVICE, count words, 4-byte aligned, or NULL: none kept */
+    int32_t max_hits;       /* K: 1 .. RT_HITS_MAX */
+    uint32_t flags;         /* RT_HITS_* */
+    int32_t waves_per_simd; /* occupancy build of the kernel: 5 / 6 / 7, or 0 = the default (7 for max_hits <= 4, else 5:
+                               profiles/hits_resources.txt) */
+    uint32_t reserved;      /* must be 0 */
+} rt_hits_params;           /* 56 B */
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_hits_params) == 56 && offsetof(rt_hits_params, rays) == 0 && offsetof(rt_hits_params, count) == 8 &&
+              offsetof(rt_hits_params, width) == 16 && offsetof(rt_hits_params, height) == 20 &&
+              offsetof(rt_hits_params, hits) == 24 && offsetof(rt_hits_params, counts) == 32 &&
+              offsetof(rt_hits_params, max_hits) == 40 && offsetof(rt_hits_params, flags) == 44 &&
+              offsetof(rt_hits_params, waves_per_simd) == 48 && offsetof(rt_hits_params, reserved) == 52,
+              "rt_hits_params");
+#endif
+
+/* Ordered hits of a batch on `stream` (a hipStream_t, NULL = null stream): stream-ordered, no synchronisation, no
+ * allocation, one kernel launch.  The scene rules are rt_trace_rays': uploaded by rt_scene_upload, a GPUScene filled
+ * by another host is rejected.  The arguments that need no device are checked first, in this order: NULL params,
+ * scene, hits; unknown flag bits or both cull flags; reserved; waves_per_simd; max_hits; the camera size (camera
+ * mode); count < 0 or > 2^31; alignment (rays and hits 16, counts 4); count 0 returns 0.  Then the scene, then the
+ * buffer sizes, then the overlaps: `hits` may not overlap `rays`, `counts` may overlap neither.  Every message begins
+ * with "rt_trace_hits: ".  Returns 0 or an error code with rt_last_error(). */
+int rt_trace_hits(const rt_hits_params* params, const GPUScene* scene, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Denoising: a viewable image from one low-sample frame and the first-hit records of its camera
@@ -1396,6 +1479,13 @@ int rt_closest_point_host(rt_scene* scene, const rt_point* points, int64_t count
 /* closest.h box_bound on the host, for tests: the lower bound of the computed d2 of every face whose vertices lie in
    the box [lo, hi] (-1: no bound), which the kernel's cull compares with the best so far. */
 float rt_closest_bound_host(const float p[3], const float lo[3], const float hi[3]);
+/* rt_trace_hits' list (csrc/hit_list.h offer, the kernel's own source) on the host, for tests: the n pairs (t[j],
+   payload[j]) offered in order to an empty list of max_hits (1 .. RT_HITS_MAX) entries under `tmax`, with the bound
+   held at tmax when count_all is not 0.  out_t / out_payload (max_hits each) receive the list, *total (may be NULL)
+   the number of offers accepted.  Payloads are opaque here and must not be 0xffffffff.  Returns the list's length,
+   or -1 with rt_last_error(). */
+int rt_hit_list_host(int max_hits, float tmax, int count_all, int64_t n, const float* t, const uint32_t* payload,
+                     float* out_t, uint32_t* out_payload, int64_t* total);
 
 /* Test hook: the private mirror built on the host from raw reference arrays (the foreign-scene path,
    rt_render on a GPUScene not uploaded by rt_scene_upload): words 10-11 of every leaf-ordered record --

@@ -9,6 +9,7 @@
     python tools/render_image.py --panorama W
     python tools/render_image.py --adaptive ROUNDS
     python tools/render_image.py --upsample S [--denoise]
+    python tools/render_image.py --hits K
 
 --aov PREFIX also writes the first-hit images of the same camera (rt.gbuffer: pixel centres, no jitter) as
 PREFIX_normal.pfm (normal * 0.5 + 0.5), PREFIX_depth.pfm (hit distance, inf on a miss) and PREFIX_albedo.pfm.
@@ -28,6 +29,9 @@ variance of the mean is largest -- and its samples per pixel as a linear grey im
 --upsample S (2, 3 or 4) renders everything above at 1/S of the config's size in each direction (a size that S does not
 divide is refused) and also writes OUT_upsampled.pfm / .ppm at the config's size: rt.upsample of the last frame, guided
 by the camera's first-hit records at both sizes.  With --denoise the low frame goes through rt.denoise first.
+--hits K (1..16) also writes OUT_hitcount.pfm: per pixel, the number of surfaces the camera ray crosses (rt.trace_hits_camera
+with RT_HITS_COUNT_ALL | RT_HITS_CULL_BACK, so that a loaded mesh's twin faces count once; K is the list kept beside the
+count) as a linear grey image -- an x-ray of the scene.
 """
 import argparse
 import os
@@ -64,6 +68,7 @@ def main():
     ap.add_argument("--panorama", type=int, default=None, metavar="W")
     ap.add_argument("--adaptive", type=int, default=None, metavar="ROUNDS")
     ap.add_argument("--upsample", type=int, default=None, metavar="S", choices=(2, 3, 4))
+    ap.add_argument("--hits", type=int, default=None, metavar="K", choices=range(1, 17))
     args = ap.parse_args()
     assert not args.variance or args.temporal is not None, "--variance needs --temporal K"
     rt = G.load_package()
@@ -144,6 +149,10 @@ def main():
         rt.write_pfm(args.out + "_samples.pfm", ao_outputs(counts.contiguous())[0], W, H)
         print(f"wrote {args.out}_adaptive.pfm / .ppm and {args.out}_samples.pfm ({args.adaptive} rounds of at most {SPP} spp after 2: "
               f"{float(counts.mean()):.2f} samples a pixel, {int(counts.min())} to {int(counts.max())})")
+    if args.hits is not None:
+        _, crossings = rt.trace_hits_camera(scene, W, H, args.hits, flags=rt.RT_HITS_COUNT_ALL | rt.RT_HITS_CULL_BACK)
+        rt.write_pfm(args.out + "_hitcount.pfm", ao_outputs(crossings.reshape(H, W).float())[0], W, H)
+        print(f"wrote {args.out}_hitcount.pfm (crossings per pixel: mean {float(crossings.float().mean()):.2f}, most {int(crossings.max())})")
     if args.aov:
         g = rt.gbuffer(scene, W, H)
         images = {"normal": g["normal"] * 0.5 + 0.5,
