@@ -60,9 +60,9 @@ static int query_scene(const char* who, const GPUScene* scene, Args* a, Variant*
 static int waves_refused(const char* who, int w) {
     return (w != 0 && (w < 5 || w > 7)) ? refuse(who, "waves_per_simd must be 0 (default), 5, 6 or 7") : 0;
 }
-static int count_refused(const char* who, int64_t count) {
+static int count_refused(const char* who, int64_t count, const char* items) {
     if (count < 0) return refuse(who, "negative count");
-    return count > (int64_t)1 << 31 ? refuse(who, "more than 2^31 rays in one call") : 0;
+    return count > (int64_t)1 << 31 ? refuse(who, std::string("more than 2^31 ") + items + " in one call") : 0;
 }
 // a short buffer would fault the GPU
 static int too_small(const char* who, const char* name, const void* p, size_t need) {
@@ -100,7 +100,7 @@ extern "C" int rt_trace_rays(const rt_trace_params* p, const GPUScene* scene, vo
     const bool camera = p->rays == nullptr;
     if (camera && (p->width <= 0 || p->height <= 0)) return refuse(who, "camera mode needs width, height > 0");
     const int64_t count = camera ? (int64_t)p->width * p->height : p->count;
-    if (count_refused(who, count) || misaligned(who, "rays and hits", 16, {p->rays, p->hits})) return 1;
+    if (count_refused(who, count, "rays") || misaligned(who, "rays and hits", 16, {p->rays, p->hits})) return 1;
     if (count == 0) return 0;
 
     QueryArgs q;
@@ -124,7 +124,7 @@ extern "C" int rt_occluded(const rt_occlusion_params* p, const GPUScene* scene, 
     if (!p->occluded) return refuse(who, "null occluded");
     if (!p->rays) return refuse(who, "null rays (there is no camera mode)");
     if (p->flags != 0) return refuse(who, "flags must be 0");
-    if (waves_refused(who, p->waves_per_simd) || count_refused(who, p->count) || misaligned(who, "rays", 16, {p->rays}))
+    if (waves_refused(who, p->waves_per_simd) || count_refused(who, p->count, "rays") || misaligned(who, "rays", 16, {p->rays}))
         return 1;
     if (p->count == 0) return 0;
 
@@ -140,11 +140,17 @@ extern "C" int rt_occluded(const rt_occlusion_params* p, const GPUScene* scene, 
     return check(launch_occlusion(v.stack, v.mode, w, a, (hipStream_t)stream), "occlusion_kernel launch");
 }
 
+// The scene of a walk launch (rt_closest.hip, rt_hits.hip) from query_scene's result.  The walk needs both halves of a
+// leaf tree: without `ltris` there is none.
+static WalkScene walk_scene(const QueryArgs& q) {
+    return {q.spheres, q.sphere_count, q.scene_fast, q.faces, q.vertices, q.nodes, q.tris, q.ltris ? q.tree : nullptr, q.ltris};
+}
+
 // The occupancy of rt_closest_point when the call asks for none, measured (profiles/closest_timing.txt, 2^20 points):
 // 7 waves per SIMD, a tie with 6 and 5 inside the spread on every batch -- config 2's scene, points uniform in the box,
 // radius inf: 7.23 vs 7.24 / 7.25 ms at 6 / 5; on the surface 5.72 vs 5.71 / 5.69; far outside 2.17 vs 2.23 / 2.25;
 // config 4's scene (leaf tree) 35.8 vs 35.6 / 35.9, 75.2 vs 73.9 / 73.7 and 9.44 vs 9.50 / 9.66 ms.  The tie is no
-// surprise: the kernel takes 59 registers and spills nothing (profiles/closest_resources.txt), so the three builds are
+// surprise: the kernel takes 60 registers and spills nothing (profiles/closest_resources.txt), so the three builds are
 // one code and each fits 8 waves; 7 stays the default, as for the ray calls on scenes without leaf trees.
 static int closest_waves(int asked) { return asked ? asked : 7; }
 
@@ -156,10 +162,9 @@ extern "C" int rt_closest_point(const rt_closest_params* p, const GPUScene* scen
     if (!p->nearest) return refuse(who, "null nearest");
     if (!p->points) return refuse(who, "null points");
     if (p->flags != 0) return refuse(who, "flags must be 0");
-    if (waves_refused(who, p->waves_per_simd)) return 1;
-    if (p->count < 0) return refuse(who, "negative count");
-    if (p->count > (int64_t)1 << 31) return refuse(who, "more than 2^31 points in one call");
-    if (misaligned(who, "points and nearest", 16, {p->points, p->nearest})) return 1;
+    if (waves_refused(who, p->waves_per_simd) || count_refused(who, p->count, "points") ||
+        misaligned(who, "points and nearest", 16, {p->points, p->nearest}))
+        return 1;
     if (p->count == 0) return 0;
 
     QueryArgs q;
@@ -170,18 +175,13 @@ extern "C" int rt_closest_point(const rt_closest_params* p, const GPUScene* scen
         return 1;
     // a lane reads its point when it starts: a record written over a later point would change it
     if (overlap(p->nearest, n * sizeof(rt_nearest), p->points, n * sizeof(rt_point))) return refuse(who, "nearest overlaps points");
-    ClosestArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.points = p->points, a.nearest = p->nearest, a.count = p->count;
-    a.spheres = q.spheres, a.sphere_count = q.sphere_count, a.scene_fast = q.scene_fast;
-    a.faces = q.faces, a.nodes = q.nodes, a.tris = q.tris;
-    a.tree = q.ltris ? q.tree : nullptr, a.ltris = q.ltris;
+    const ClosestArgs a{p->points, p->nearest, p->count, walk_scene(q)};
     return check(launch_closest(v.stack, closest_waves(p->waves_per_simd), a, (hipStream_t)stream), "closest_kernel launch");
 }
 
 // The occupancy of rt_trace_hits when the call asks for none, from the compiler's figures (profiles/hits_resources.txt):
 // the 4-slot list takes 71 registers and spills nothing, so its three builds are one code and run at 7 like the other
-// ray calls; the 8- and 16-slot lists spill least at 5 (0 and 38 vector registers, against 26 and 162 at 7).
+// ray calls; the 8- and 16-slot lists spill least at 5 (0 and 29 vector registers, against 26 and 171 at 7).
 // tools/hits_timing.py measures the choice (profiles/hits_timing.txt).
 static int hits_waves(int asked, int max_hits) { return asked ? asked : max_hits <= 4 ? 7 : 5; }
 
@@ -201,7 +201,7 @@ extern "C" int rt_trace_hits(const rt_hits_params* p, const GPUScene* scene, voi
     const bool camera = p->rays == nullptr;
     if (camera && (p->width <= 0 || p->height <= 0)) return refuse(who, "camera mode needs width, height > 0");
     const int64_t count = camera ? (int64_t)p->width * p->height : p->count;
-    if (count_refused(who, count) || misaligned(who, "rays and hits", 16, {p->rays, p->hits}) ||
+    if (count_refused(who, count, "rays") || misaligned(who, "rays and hits", 16, {p->rays, p->hits}) ||
         misaligned(who, "counts", 4, {p->counts}))
         return 1;
     if (count == 0) return 0;
@@ -217,14 +217,8 @@ extern "C" int rt_trace_hits(const rt_hits_params* p, const GPUScene* scene, voi
     if (overlap(p->hits, hit_bytes, p->rays, n * sizeof(rt_ray))) return refuse(who, "hits overlaps rays");
     if (overlap(p->counts, n * 4, p->rays, n * sizeof(rt_ray))) return refuse(who, "counts overlaps rays");
     if (overlap(p->counts, n * 4, p->hits, hit_bytes)) return refuse(who, "counts overlaps hits");
-    HitsArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.rays = p->rays, a.hits = p->hits, a.counts = p->counts, a.count = count;
-    a.width = camera ? p->width : 1, a.height = camera ? p->height : 1, a.cam = q.cam;
-    a.max_hits = p->max_hits, a.flags = p->flags;
-    a.spheres = q.spheres, a.sphere_count = q.sphere_count, a.scene_fast = q.scene_fast;
-    a.faces = q.faces, a.vertices = q.vertices, a.nodes = q.nodes, a.tris = q.tris;
-    a.tree = q.ltris ? q.tree : nullptr, a.ltris = q.ltris;
+    const HitsArgs a{p->rays, p->hits, p->counts, count, camera ? p->width : 1, camera ? p->height : 1, q.cam,
+                     p->max_hits, p->flags, walk_scene(q)};
     return check(launch_hits(v.stack, hits_waves(p->waves_per_simd, p->max_hits), a, (hipStream_t)stream), "hits_kernel launch");
 }
 
@@ -277,7 +271,7 @@ extern "C" int rt_radiance(const rt_radiance_params* p, const GPUScene* scene, v
     if (!p->rng) return refuse(who, "null rng");
     if (!p->radiance) return refuse(who, "null radiance");
     if (p->flags != 0) return refuse(who, "flags must be 0");
-    if (waves_refused(who, p->waves_per_simd) || count_refused(who, p->count)) return 1;
+    if (waves_refused(who, p->waves_per_simd) || count_refused(who, p->count, "rays")) return 1;
     if (p->bounces < 0) return refuse(who, "bounces must be >= 0");
     if (p->samples < 1 || p->samples > (1 << 24)) return refuse(who, "samples must be 1..2^24");
     if (misaligned(who, "rays and radiance", 16, {p->rays, p->radiance}) || misaligned(who, "rng", 8, {p->rng})) return 1;
@@ -319,7 +313,7 @@ extern "C" int rt_sample_pixels(const rt_sample_pixels_params* p, const GPUScene
     if (!p->accum) return refuse(who, "null accum");
     if (p->flags != 0) return refuse(who, "flags must be 0");
     if (p->reserved != 0) return refuse(who, "reserved must be 0");
-    if (waves_refused(who, p->waves_per_simd) || count_refused(who, p->count)) return 1;
+    if (waves_refused(who, p->waves_per_simd) || count_refused(who, p->count, "rays")) return 1;
     if (p->width <= 0 || p->height <= 0) return refuse(who, "width and height must be > 0");
     const int64_t pixel_count = (int64_t)p->width * p->height;
     if (pixel_count > (int64_t)1 << 30) return refuse(who, "more than 2^30 pixels");

@@ -14,11 +14,10 @@
 // mirror's `fast` range -- the lane walks everything and culls nothing: the same answer, slowly.  A NaN radius accepts
 // nothing (d2 <= NaN is false), so such a lane skips the walk.
 //
-// Against the shape first planned for this unit: the frame is not RT_TRACE_FRAME -- this body never calls rtfast::trace, so it
-// declares the stack's LDS rows alone (no deferral or leaf-tree scratch) -- and the kernels have no MODE: whether a
-// leaf has a tree is read from its lead record.  The stack is rtfast::Stack (16 entries in LDS, deeper ones private),
-// its 30 / 40 / 64 size chosen from the mirror's depth as for the ray kernels: near-first descent pushes one entry
-// per level at most.  5 / 6 / 7 waves per SIMD as the other batch units (profiles/closest_resources.txt).
+// The kernels are a walk unit's (rt_batch.h RT_WALK_KERNELS, no build integer of their own).  The stack is
+// rtfast::Stack (16 entries in LDS, deeper ones private), its 30 / 40 / 64 size chosen from the mirror's depth as for
+// the ray kernels: near-first descent pushes one entry per level at most.  5 / 6 / 7 waves per SIMD as the other batch
+// units (profiles/closest_resources.txt).
 #include "rt_batch.h"
 #include "closest.h"
 
@@ -66,7 +65,7 @@ __device__ __forceinline__ void tree_leaf(Walk& w, const float4* tree, const flo
     }
 }
 
-template <int STACK>
+template <int STACK, int>
 __device__ __forceinline__ void closest_body(const ClosestArgs& a, const rtfast::Stack<RT_BATCH_SL(STACK)>& stk) {
     using S = rtfast::Stack<RT_BATCH_SL(STACK)>;
     const long long i = (long long)blockIdx.x * WAVE + (long long)(threadIdx.x & 63u);
@@ -74,16 +73,16 @@ __device__ __forceinline__ void closest_body(const ClosestArgs& a, const rtfast:
     const float4 P = reinterpret_cast<const float4*>(a.points)[i];
     Walk w;
     w.p = rtm::mk(P.x, P.y, P.z);
-    w.cull = a.scene_fast != 0 && rtc::point_in_cull_range(w.p);
+    w.cull = a.s.scene_fast != 0 && rtc::point_in_cull_range(w.p);
     const float r2 = P.w * P.w;
     w.best = rtc::best_start(r2);
     if (r2 == r2) {
-        for (int k = 0; k < a.sphere_count; k++) {
-            const GeometrySphere& sp = a.spheres[k];
+        for (int k = 0; k < a.s.sphere_count; k++) {
+            const GeometrySphere& sp = a.s.spheres[k];
             rtc::offer(w.best, rtc::closest_on_sphere(w.p, ld3(sp.position), sp.radius), 1u, (uint32_t)k);
         }
-        const float4* const nodes4 = reinterpret_cast<const float4*>(a.nodes);
-        const float4* const tris = reinterpret_cast<const float4*>(a.tris);
+        const float4* const nodes4 = reinterpret_cast<const float4*>(a.s.nodes);
+        const float4* const tris = reinterpret_cast<const float4*>(a.s.tris);
         int sp = S::empty((int)(threadIdx.x & 63u));
         const float4 rlo = ldo(nodes4, 0), rhi = ldo(nodes4, 1);
         uint32_t first = __float_as_uint(rhi.z), count = __float_as_uint(rhi.w);
@@ -92,10 +91,10 @@ __device__ __forceinline__ void closest_body(const ClosestArgs& a, const rtfast:
             bool step = false;  // whether (first, count) names the next node
             if (count > 0) {
                 bool walked = false;
-                if (count > (uint32_t)rtfast::BIG && a.tree) {  // a big leaf's lead record says whether it has a tree
+                if (count > (uint32_t)rtfast::BIG && a.s.tree) {  // a big leaf's lead record says whether it has a tree
                     const float4 lead = ldo(tris, 3 * first + 2);
                     if (__float_as_uint(lead.w) == 2u) {
-                        tree_leaf(w, a.tree, a.ltris, __float_as_uint(lead.z));
+                        tree_leaf(w, a.s.tree, a.s.ltris, __float_as_uint(lead.z));
                         walked = true;
                     }
                 }
@@ -133,7 +132,7 @@ __device__ __forceinline__ void closest_body(const ClosestArgs& a, const rtfast:
     const Best& b = w.best;
     float4 o0 = make_float4(P.w, 0.0f, 0.0f, 0.0f), o1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (b.kind != 0u) {
-        const uint32_t material = b.kind == 1u ? (uint32_t)a.spheres[b.id].material : a.faces[b.id].material;
+        const uint32_t material = b.kind == 1u ? (uint32_t)a.s.spheres[b.id].material : a.s.faces[b.id].material;
         o0 = make_float4(sqrtf(b.d2), __uint_as_float(b.kind), __uint_as_float(b.id), __uint_as_float(material));
         o1 = make_float4(b.q.x, b.q.y, b.q.z, __uint_as_float(b.region));
     }
@@ -142,34 +141,12 @@ __device__ __forceinline__ void closest_body(const ClosestArgs& a, const rtfast:
     out[1] = o1;
 }
 
-#define RT_CLOSEST_KERNEL(W) \
-    template <int STACK> \
-    __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(W))) void closest_kernel_w##W(ClosestArgs a) { \
-        constexpr int SL = RT_BATCH_SL(STACK); \
-        __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE]; \
-        uint32_t ovf[STACK > SL ? STACK - SL : 1]; \
-        closest_body<STACK>(a, rtfast::Stack<SL>{stack_lds, ovf}); \
-    }
-RT_CLOSEST_KERNEL(5)
-RT_CLOSEST_KERNEL(6)
-RT_CLOSEST_KERNEL(7)
-#undef RT_CLOSEST_KERNEL
-
-template <int STACK>
-auto closest_kernel(int w) -> void (*)(ClosestArgs) {
-    return w == 7 ? closest_kernel_w7<STACK> : w == 6 ? closest_kernel_w6<STACK> : closest_kernel_w5<STACK>;
-}
+RT_WALK_KERNELS(closest_kernel, ClosestArgs, closest_body)
 
 }  // namespace
 
-// One wave per 64 of a.count points: stack 30 / 40 / 64 (rt_variant.h variant_stack), then the occupancy.
 hipError_t launch_closest(int stack, int waves_per_simd, const ClosestArgs& a, hipStream_t s) {
-    if (a.count <= 0 || a.count > (1LL << 31)) return hipErrorInvalidValue;
-    void (*const k)(ClosestArgs) = stack == 30 ? closest_kernel<30>(waves_per_simd)
-                                   : stack == 40 ? closest_kernel<40>(waves_per_simd)
-                                                 : closest_kernel<64>(waves_per_simd);
-    hipLaunchKernelGGL(k, dim3((unsigned)((a.count + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, a);
-    return hipGetLastError();
+    return launch_walk<closest_kernel_set, 0>(stack, waves_per_simd, a.count, a, s);
 }
 
 }  // namespace rtk

@@ -102,18 +102,34 @@ struct Hit {
 };
 
 // Triangle records: A = (v0.xyz, e1.x), B = (e1.yz, e2.xy), C = (e2.z, face, -, -).
-// glm::intersectRayTriangle (gtx/intersect.inl:29-94) as a predicate + the rare accept.
+// glm::intersectRayTriangle's quantities (gtx/intersect.inl:29-94) for one record, in its operation order: the four the
+// accept predicate reads (tri_ok), and e2 and perp, from which an accepted triangle's distance is
+// dot(e2, perp) / det and its barycentrics u / det, v / det.
+struct TriEval {
+    float det, u, v, uv;
+    f3 e2, perp;
+};
+__device__ __forceinline__ TriEval tri_eval(f3 o, f3 nd, float4 A, float4 B, float4 Cc) {
+    TriEval E;
+    const f3 e1 = rtm::mk(A.w, B.x, B.y);
+    E.e2 = rtm::mk(B.z, B.w, Cc.x);
+    const f3 p = rtm::cross(nd, E.e2);
+    E.det = rtm::dot(e1, p);
+    const f3 dist = rtm::sub(o, rtm::mk(A.x, A.y, A.z));
+    E.u = rtm::dot(dist, p);
+    E.perp = rtm::cross(dist, e1);
+    E.v = rtm::dot(nd, E.perp);
+    E.uv = E.u + E.v;
+    return E;
+}
+
+// ... as a predicate + the rare accept.
 template <bool STATS, class C>
 __device__ __forceinline__ void test_triangle(const Ray& R, float4 A, float4 B, float4 Cc, Hit& h, C& c) {
     const float eps = 1.1920928955078125e-07f;
-    const f3 e1 = rtm::mk(A.w, B.x, B.y), e2 = rtm::mk(B.z, B.w, Cc.x);
-    const f3 p = rtm::cross(R.nd, e2);
-    const float det = rtm::dot(e1, p);
-    const f3 dist = rtm::sub(R.o, rtm::mk(A.x, A.y, A.z));
-    const float u = rtm::dot(dist, p);
-    const f3 perp = rtm::cross(dist, e1);
-    const float v = rtm::dot(R.nd, perp);
-    const float uv = u + v;
+    const TriEval E = tri_eval(R.o, R.nd, A, B, Cc);
+    const float det = E.det, u = E.u, v = E.v, uv = E.uv;
+    const f3 e2 = E.e2, perp = E.perp;
     // det > eps: !(u < 0 || u > det) && !(v < 0 || u+v > det); det < -eps: the same with every
     // inequality reversed.  Flipping the signs of u, v, u+v and det by det's sign bit maps the
     // second case onto the first exactly (negation is exact; NaN compares stay false).
@@ -311,22 +327,15 @@ RT_HD bool tri_ok_folded(float adet, float su, float sv, float suv) {
 // a min-reduction would not, so such a ray is redone sequentially).
 __device__ __forceinline__ bool tri_accept(f3 o, f3 nd, float4 A, float4 B, float4 Cc, float best, float* t_o,
                                            float* bx, float* by, bool* nan) {
-    const f3 e1 = rtm::mk(A.w, B.x, B.y), e2 = rtm::mk(B.z, B.w, Cc.x);
-    const f3 p = rtm::cross(nd, e2);
-    const float det = rtm::dot(e1, p);
-    const f3 dist = rtm::sub(o, rtm::mk(A.x, A.y, A.z));
-    const float u = rtm::dot(dist, p);
-    const f3 perp = rtm::cross(dist, e1);
-    const float v = rtm::dot(nd, perp);
-    const float uv = u + v;
-    if (!tri_ok(det, u, v, uv)) return false;
-    const float inv_det = 1.0f / det;
-    const float t = rtm::dot(e2, perp) * inv_det;
+    const TriEval E = tri_eval(o, nd, A, B, Cc);
+    if (!tri_ok(E.det, E.u, E.v, E.uv)) return false;
+    const float inv_det = 1.0f / E.det;
+    const float t = rtm::dot(E.e2, E.perp) * inv_det;
     *nan = *nan || (t != t);
     if (t >= best || t < 0.0f) return false;
     *t_o = t;
-    *bx = u * inv_det;
-    *by = v * inv_det;
+    *bx = E.u * inv_det;
+    *by = E.v * inv_det;
     return true;
 }
 
@@ -808,16 +817,11 @@ struct LeafBest {
 
 // glm::intersectRayTriangle as in test_triangle, candidate kept by (t, index).
 __device__ __forceinline__ void leaf_candidate(const Ray& R, float4 A, float4 B, float4 Cc, LeafBest& L) {
-    const f3 e1 = rtm::mk(A.w, B.x, B.y), e2 = rtm::mk(B.z, B.w, Cc.x);
-    const f3 p = rtm::cross(R.nd, e2);
-    const float det = rtm::dot(e1, p);
-    const f3 dist = rtm::sub(R.o, rtm::mk(A.x, A.y, A.z));
-    const float u = rtm::dot(dist, p);
-    const f3 perp = rtm::cross(dist, e1);
-    const float v = rtm::dot(R.nd, perp);
-    if (tri_ok(det, u, v, u + v)) {
+    const TriEval E = tri_eval(R.o, R.nd, A, B, Cc);
+    const float det = E.det, u = E.u, v = E.v;
+    if (tri_ok(det, u, v, E.uv)) {
         const float inv_det = 1.0f / det;
-        const float t = rtm::dot(e2, perp) * inv_det;
+        const float t = rtm::dot(E.e2, E.perp) * inv_det;
         const uint32_t j = __float_as_uint(Cc.z);
         L.nan = L.nan || (t != t);
         if (t >= 0.0f && (t < L.t || (t == L.t && L.found && j < L.j))) {

@@ -4,13 +4,13 @@
 // under RT_HITS_COUNT_ALL -- stands wherever the reference reads `closest`.
 //
 // One ray per lane, wave w owning rays [64w, 64w + 64) as the ray-batch units (rt_batch.h); lanes past `count` leave at
-// once and nothing here is wave-cooperative, so the frame is the stack's LDS rows alone (as rt_closest.hip: no
-// RT_TRACE_FRAME, no MODE).  The walk is rt_fast.h's own pieces on the mirror's private nodes: make_ray, the root as
+// once and nothing here is wave-cooperative, so the kernels are a walk unit's (rt_batch.h RT_WALK_KERNELS, their build
+// integer the list's capacity).  The walk is rt_fast.h's own pieces on the mirror's private nodes: make_ray, the root as
 // trav_begin tests it, inner_step and pop with `best` = the list's bound at that moment -- so every node decision is
 // the reference's, the IEEE quotients outside the filtered range included.  Leaves of every size read the contiguous
-// 48-byte `tris` records with the branch-free predicate (tri_ok); only an accepted triangle pays the division.  A
-// leaf with a leaf tree (mirror.h pf == 2) is walked through `tree` / `ltris` in pre-order by its skip links, culling
-// with cluster_cull against the bound, which drops as the walk fills the list.
+// 48-byte `tris` records with the branch-free predicate (tri_eval, tri_ok); only an accepted triangle pays the
+// division.  A leaf with a leaf tree (mirror.h pf == 2) is walked through `tree` / `ltris` in pre-order by its skip
+// links, culling with cluster_cull against the bound, which drops as the walk fills the list.
 //
 // Why order within a leaf is free.  After K offers the list holds the K smallest of everything offered so far under
 // the order (t, arrival), and an offer that is refused would have been cut anyway -- so the list after a leaf depends
@@ -41,25 +41,6 @@ namespace {
 using rtfast::ldo;
 using rtm::f3;
 
-// glm::intersectRayTriangle's quantities for one record (test_triangle's operation order).
-struct TriEval {
-    float det, u, v, uv;
-    f3 e2, perp;
-};
-__device__ __forceinline__ TriEval tri_eval(const rtfast::Ray& R, float4 A, float4 B, float4 Cc) {
-    TriEval E;
-    const f3 e1 = rtm::mk(A.w, B.x, B.y);
-    E.e2 = rtm::mk(B.z, B.w, Cc.x);
-    const f3 p = rtm::cross(R.nd, E.e2);
-    E.det = rtm::dot(e1, p);
-    const f3 dist = rtm::sub(R.o, rtm::mk(A.x, A.y, A.z));
-    E.u = rtm::dot(dist, p);
-    E.perp = rtm::cross(dist, e1);
-    E.v = rtm::dot(R.nd, E.perp);
-    E.uv = E.u + E.v;
-    return E;
-}
-
 struct Walk {
     rtfast::Ray R;
     uint32_t cull;  // RT_HITS_CULL_BACK / RT_HITS_CULL_FRONT, or 0
@@ -70,7 +51,7 @@ struct Walk {
 template <int CAP>
 __device__ __forceinline__ void offer_record(const Walk& w, rth::List<CAP>& L, float4 A, float4 B, float4 Cc, uint32_t idx,
                                              uint32_t leaf_end) {
-    const TriEval E = tri_eval(w.R, A, B, Cc);
+    const rtfast::TriEval E = rtfast::tri_eval(w.R.o, w.R.nd, A, B, Cc);
     // |det| > eps for every triangle the test accepts: the sign is never in doubt
     const bool wound = w.cull == 0u || ((E.det > 0.0f) == (w.cull == RT_HITS_CULL_BACK));
     if (rtfast::tri_ok(E.det, E.u, E.v, E.uv) && wound) {
@@ -108,12 +89,7 @@ __device__ __forceinline__ void tree_leaf(const Walk& w, rth::List<CAP>& L, cons
     }
 }
 
-// One row of the output: three 16-byte stores.
-__device__ __forceinline__ void store_row(float4* out, float4 a, float4 b, float4 c) {
-    out[0] = a, out[1] = b, out[2] = c;
-}
-
-template <int CAP, int STACK>
+template <int STACK, int CAP>
 __device__ __forceinline__ void hits_body(const HitsArgs& a, const rtfast::Stack<RT_BATCH_SL(STACK)>& stk) {
     using S = rtfast::Stack<RT_BATCH_SL(STACK)>;
     const long long i = (long long)blockIdx.x * WAVE + (long long)(threadIdx.x & 63u);
@@ -123,7 +99,7 @@ __device__ __forceinline__ void hits_body(const HitsArgs& a, const rtfast::Stack
     query_ray(a, i, ro, rd, tmax);
     const f3 nd = rtm::normalize(rd);
     Walk w;
-    w.R = rtfast::make_ray(ro, rd, nd, a.scene_fast != 0);
+    w.R = rtfast::make_ray(ro, rd, nd, a.s.scene_fast != 0);
     w.cull = a.flags & (RT_HITS_CULL_BACK | RT_HITS_CULL_FRONT);
     w.all = (a.flags & RT_HITS_COUNT_ALL) != 0;
     const int K = a.max_hits;
@@ -131,15 +107,15 @@ __device__ __forceinline__ void hits_body(const HitsArgs& a, const rtfast::Stack
     rth::init(L, K, tmax);
 
     // GetRayHit's sphere loop (main_raytracing.cu:87-101): one distance per sphere, never culled
-    for (int k = 0; k < a.sphere_count; k++) {
-        const GeometrySphere& sp = a.spheres[k];
+    for (int k = 0; k < a.s.sphere_count; k++) {
+        const GeometrySphere& sp = a.s.spheres[k];
         float dist;
         if (rtd::intersect_sphere(ro, nd, ld3(sp.position), sp.radius * sp.radius, &dist)) rth::offer(L, w.all, dist, rth::SPHERE | (uint32_t)k);
     }
 
     // BVHRayHit: the root as trav_begin tests it, then inner_step / pop against the list's bound
-    const float4* const nodes4 = reinterpret_cast<const float4*>(a.nodes);
-    const float4* const tris = reinterpret_cast<const float4*>(a.tris);
+    const float4* const nodes4 = reinterpret_cast<const float4*>(a.s.nodes);
+    const float4* const tris = reinterpret_cast<const float4*>(a.s.tris);
     int sp = S::empty((int)(threadIdx.x & 63u));
     uint32_t first, count;
     bool go;
@@ -155,10 +131,10 @@ __device__ __forceinline__ void hits_body(const HitsArgs& a, const rtfast::Stack
         bool step = false;
         if (count > 0) {
             bool walked = false;
-            if (count > (uint32_t)rtfast::BIG && a.tree) {  // a big leaf's lead record says whether it has a tree
+            if (count > (uint32_t)rtfast::BIG && a.s.tree) {  // a big leaf's lead record says whether it has a tree
                 const float4 lead = ldo(tris, 3 * first + 2);
                 if (__float_as_uint(lead.w) == 2u) {
-                    tree_leaf(w, L, a.tree, a.ltris, __float_as_uint(lead.z), first, count);
+                    tree_leaf(w, L, a.s.tree, a.s.ltris, __float_as_uint(lead.z), first, count);
                     walked = true;
                 }
             }
@@ -171,8 +147,8 @@ __device__ __forceinline__ void hits_body(const HitsArgs& a, const rtfast::Stack
     }
 
     // The rows: the list's slots in turn (rotate: no runtime index), the first CAP - K of which hold no entry.  An
-    // entry becomes the record rt_trace_rays writes for that primitive and t (rt_query.hip: same arithmetic, same
-    // flip); every other row is its miss record.
+    // entry becomes the record rt_trace_rays writes for that primitive and t (rt_batch.h store_hit); every other row
+    // is its miss record.
     float4* const out = reinterpret_cast<float4*>(a.hits) + 3 * ((size_t)i * (size_t)K);
     uint32_t held = 0;
 #pragma unroll 1
@@ -183,68 +159,32 @@ __device__ __forceinline__ void hits_body(const HitsArgs& a, const rtfast::Stack
         if (s < CAP - K) continue;
         float4* const row = out + 3 * (s - (CAP - K));
         if (p == rth::EMPTY) {
-            store_row(row, make_float4(tmax, 0.0f, 0.0f, 0.0f), make_float4(0.0f, 0.0f, 0.0f, 0.0f), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+            store_miss(row, tmax);
             continue;
         }
         held++;
-        const f3 pos = rtm::add(ro, rtm::muls(nd, t));
         if (p & rth::SPHERE) {
-            const uint32_t id = p & ~rth::SPHERE;
-            const GeometrySphere& sph = a.spheres[id];
-            const f3 nrm = rtm::divs(rtm::sub(pos, ld3(sph.position)), sph.radius);
-            store_row(row, make_float4(t, __uint_as_float(1u), __uint_as_float(id), __uint_as_float((uint32_t)sph.material)),
-                      make_float4(nrm.x, nrm.y, nrm.z, 0.0f), make_float4(pos.x, pos.y, pos.z, 0.0f));
-        } else {
+            store_hit(row, ro, nd, t, 1u, p & ~rth::SPHERE, 0.0f, 0.0f, a.s.spheres, a.s.faces, a.s.vertices);
+        } else {  // the test on the record again: the same operations give the same bits
             const float4 Cc = ldo(tris, 3 * p + 2);
-            const TriEval E = tri_eval(w.R, ldo(tris, 3 * p), ldo(tris, 3 * p + 1), Cc);
+            const rtfast::TriEval E = rtfast::tri_eval(w.R.o, w.R.nd, ldo(tris, 3 * p), ldo(tris, 3 * p + 1), Cc);
             const float inv_det = 1.0f / E.det;
-            const float bx = E.u * inv_det, by = E.v * inv_det;
-            const uint32_t id = __float_as_uint(Cc.y);
-            const GPUFace f = a.faces[id];
-            const float bz = (1.0f - bx) - by;
-            f3 nrm = rtm::normalize(rtm::add(rtm::add(rtm::muls(ld3(a.vertices[f.v0].normal), bx), rtm::muls(ld3(a.vertices[f.v1].normal), by)),
-                                             rtm::muls(ld3(a.vertices[f.v2].normal), bz)));
-            if (rtm::dot(nd, nrm) >= 0.0f) nrm = rtm::neg(nrm);
-            store_row(row, make_float4(t, __uint_as_float(2u), __uint_as_float(id), __uint_as_float(f.material)),
-                      make_float4(nrm.x, nrm.y, nrm.z, bx), make_float4(pos.x, pos.y, pos.z, by));
+            store_hit(row, ro, nd, t, 2u, __float_as_uint(Cc.y), E.u * inv_det, E.v * inv_det, a.s.spheres, a.s.faces, a.s.vertices);
         }
     }
     if (a.counts) a.counts[i] = w.all ? L.total : held;
 }
 
-#define RT_HITS_KERNEL(W) \
-    template <int CAP, int STACK> \
-    __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(W))) void hits_kernel_w##W(HitsArgs a) { \
-        constexpr int SL = RT_BATCH_SL(STACK); \
-        __shared__ uint32_t stack_lds[(SL + rtfast::STACK_PAD_ROWS) * WAVE]; \
-        uint32_t ovf[STACK > SL ? STACK - SL : 1]; \
-        hits_body<CAP, STACK>(a, rtfast::Stack<SL>{stack_lds, ovf}); \
-    }
-RT_HITS_KERNEL(5)
-RT_HITS_KERNEL(6)
-RT_HITS_KERNEL(7)
-#undef RT_HITS_KERNEL
-
-template <int CAP, int STACK>
-auto hits_kernel(int w) -> void (*)(HitsArgs) {
-    return w == 7 ? hits_kernel_w7<CAP, STACK> : w == 6 ? hits_kernel_w6<CAP, STACK> : hits_kernel_w5<CAP, STACK>;
-}
-template <int CAP>
-auto hits_kernel(int stack, int w) -> void (*)(HitsArgs) {
-    return stack == 30 ? hits_kernel<CAP, 30>(w) : stack == 40 ? hits_kernel<CAP, 40>(w) : hits_kernel<CAP, 64>(w);
-}
+RT_WALK_KERNELS(hits_kernel, HitsArgs, hits_body)
 
 }  // namespace
 
-// One wave per 64 of a.count rays: the list capacity that holds max_hits, then the stack (rt_variant.h variant_stack),
-// then the occupancy.
+// The list capacity that holds max_hits, then launch_walk's choices.
 hipError_t launch_hits(int stack, int waves_per_simd, const HitsArgs& a, hipStream_t s) {
-    if (a.count <= 0 || a.count > (1LL << 31) || a.max_hits < 1 || a.max_hits > rth::MAX_HITS) return hipErrorInvalidValue;
-    void (*const k)(HitsArgs) = a.max_hits <= 4   ? hits_kernel<4>(stack, waves_per_simd)
-                                : a.max_hits <= 8 ? hits_kernel<8>(stack, waves_per_simd)
-                                                  : hits_kernel<16>(stack, waves_per_simd);
-    hipLaunchKernelGGL(k, dim3((unsigned)((a.count + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, a);
-    return hipGetLastError();
+    if (a.max_hits < 1 || a.max_hits > rth::MAX_HITS) return hipErrorInvalidValue;
+    return a.max_hits <= 4   ? launch_walk<hits_kernel_set, 4>(stack, waves_per_simd, a.count, a, s)
+           : a.max_hits <= 8 ? launch_walk<hits_kernel_set, 8>(stack, waves_per_simd, a.count, a, s)
+                             : launch_walk<hits_kernel_set, 16>(stack, waves_per_simd, a.count, a, s);
 }
 
 }  // namespace rtk

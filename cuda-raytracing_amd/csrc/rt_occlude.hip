@@ -17,23 +17,11 @@ namespace {
 template <int STACK, int MODE>
 __device__ __forceinline__ bool occluded(const QueryArgs& q, const rtfast::Stack<RT_BATCH_SL(STACK)>& stk,
                                          uint32_t* const scratch, rtm::f3 ro, rtm::f3 rd, float tmax, bool live) {
-    // GetRayHit's sphere loop (main_raytracing.cu:87-101) as in query_body: in order and to the end, since a
-    // later sphere overrides an earlier one whenever `dist >= best` is false
+    // GetRayHit's sphere loop as in query_body
     rtfast::Hit h;
     h.best = tmax, h.kind = 0, h.id = 0, h.bx = h.by = 0.0f;
     const rtm::f3 nd = rtm::normalize(rd);
-    if (live) {
-        for (int k = 0; k < q.sphere_count; k++) {
-            const GeometrySphere& sp = q.spheres[k];
-            float dist;
-            if (rtd::intersect_sphere(ro, nd, ld3(sp.position), sp.radius * sp.radius, &dist)) {
-                if (dist >= h.best) continue;
-                h.best = dist;
-                h.kind = 1;
-                h.id = (uint32_t)k;
-            }
-        }
-    }
+    if (live) h = sphere_loop(q, ro, nd, h);
     rtfast::Ray R = rtfast::make_ray(ro, rd, nd, q.scene_fast != 0);
     // a sphere's hit below tmax inside the gate is final: the traversal could only replace it by a closer one.
     // (A sphere's hit that is not below tmax -- tmax NaN -- traverses as a closest-hit lane: trace stops only

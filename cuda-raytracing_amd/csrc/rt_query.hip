@@ -22,18 +22,7 @@ __device__ __forceinline__ void query_body(const QueryArgs& q, const rtfast::Sta
     rtfast::Hit h;
     h.best = tmax, h.kind = 0, h.id = 0, h.bx = h.by = 0.0f;
     rtm::f3 nd = rtm::normalize(rd);
-    if (live) {
-        for (int k = 0; k < q.sphere_count; k++) {
-            const GeometrySphere& sp = q.spheres[k];
-            float dist;
-            if (rtd::intersect_sphere(ro, nd, ld3(sp.position), sp.radius * sp.radius, &dist)) {
-                if (dist >= h.best) continue;
-                h.best = dist;
-                h.kind = 1;
-                h.id = (uint32_t)k;
-            }
-        }
-    }
+    if (live) h = sphere_loop(q, ro, nd, h);
     rtfast::Ray R = rtfast::make_ray(ro, rd, nd, q.scene_fast != 0);
     Counters c;
     rtfast::trace<false, MODE>(reinterpret_cast<const float4*>(q.nodes), reinterpret_cast<const float4*>(q.tris), q.pairs,
@@ -41,37 +30,15 @@ __device__ __forceinline__ void query_body(const QueryArgs& q, const rtfast::Sta
                                q.face_leaf);
     if (!live) return;
 
-    // the record: three 16-byte stores, adjacent lanes to adjacent records
+    // the record (rt_batch.h store_hit)
     query_ray(q, i, ro, rd, tmax);
     nd = rtm::normalize(rd);
     float4* const out = reinterpret_cast<float4*>(q.hits + i);
     // `result.distance < max_distance` (main_raytracing.cu:108): a NaN distance is a miss
-    if (h.kind != 0 && h.best < tmax) {
-        // the attributes of shade_segment (rt_fast_body.h), same arithmetic
-        const rtm::f3 pos = rtm::add(ro, rtm::muls(nd, h.best));
-        rtm::f3 nrm;
-        uint32_t mat;
-        if (h.kind == 1) {
-            const GeometrySphere& sp = q.spheres[h.id];
-            nrm = rtm::divs(rtm::sub(pos, ld3(sp.position)), sp.radius);
-            mat = (uint32_t)sp.material;
-        } else {
-            const GPUFace f = q.faces[h.id];
-            const float bz = (1.0f - h.bx) - h.by;
-            nrm = rtm::normalize(rtm::add(rtm::add(rtm::muls(ld3(q.vertices[f.v0].normal), h.bx),
-                                                   rtm::muls(ld3(q.vertices[f.v1].normal), h.by)),
-                                          rtm::muls(ld3(q.vertices[f.v2].normal), bz)));
-            if (rtm::dot(nd, nrm) >= 0.0f) nrm = rtm::neg(nrm);
-            mat = f.material;
-        }
-        out[0] = make_float4(h.best, __uint_as_float((uint32_t)h.kind), __uint_as_float(h.id), __uint_as_float(mat));
-        out[1] = make_float4(nrm.x, nrm.y, nrm.z, h.bx);
-        out[2] = make_float4(pos.x, pos.y, pos.z, h.by);
-    } else {
-        out[0] = make_float4(tmax, 0.0f, 0.0f, 0.0f);
-        out[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        out[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
+    if (h.kind != 0 && h.best < tmax)
+        store_hit(out, ro, nd, h.best, (uint32_t)h.kind, h.id, h.bx, h.by, q.spheres, q.faces, q.vertices);
+    else
+        store_miss(out, tmax);
 }
 
 RT_BATCH_KERNELS(query_kernel, QueryArgs, query_body)

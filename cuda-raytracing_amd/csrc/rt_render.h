@@ -113,27 +113,34 @@ struct SampleArgs {
 static_assert(offsetof(SampleArgs, r) == 0, "the kernel-argument segment starts with the RenderArgs");
 hipError_t launch_sample_pixels(int stack, int mode, int waves_per_simd, const SampleArgs& a, hipStream_t s);
 
-// The closest-point kernel (rt_closest.hip, rt_closest_point): one point per lane over the mirror's private nodes,
-// leaf-ordered records and leaf trees, culling by distance to a box (closest.h).  No MODE: stack 30 / 40 / 64 and the
-// occupancy alone choose the build.
-struct ClosestArgs {
-    const rt_point* points;
-    rt_nearest* nearest;
-    long long count;
+// The scene as the walk kernels read it (rt_closest.hip, rt_hits.hip: rt_batch.h RT_WALK_KERNELS), each lane walking the
+// mirror's private nodes, leaf-ordered records and leaf trees itself: query_scene's result without the arrays only
+// rtfast::trace reads (rt_batch_calls.hip walk_scene).
+struct WalkScene {
     const GeometrySphere* spheres;
     int sphere_count;
-    int scene_fast;  // every node bound inside the mirror's `fast` range: closest.h box_bound's premise on the boxes
-    const GPUFace* faces;  // the winner's material
+    int scene_fast;  // every node bound inside the mirror's `fast` range: the premise of the culls' bounds on the boxes
+    const GPUFace* faces;
+    const GPUVertex* vertices;
     const GPUBVHNode* nodes;  // the mirror's private node array
     const FlatTri* tris;
     const float4 *tree, *ltris;  // null: the scene has no leaf tree
 };
+
+// The closest-point kernel (rt_closest.hip, rt_closest_point): one point per lane, culling by distance to a box
+// (closest.h).  Stack 30 / 40 / 64 and the occupancy choose the build.
+struct ClosestArgs {
+    const rt_point* points;
+    rt_nearest* nearest;
+    long long count;
+    WalkScene s;  // faces: the winner's material; vertices unused
+};
 hipError_t launch_closest(int stack, int waves_per_simd, const ClosestArgs& a, hipStream_t s);
 
-// The ordered-hits kernel (rt_hits.hip, rt_trace_hits): one ray per lane, a per-lane walk of the mirror's private nodes
-// with the rt_fast.h pieces (make_ray, inner_step, pop), the first max_hits accepted distances kept in a register list
-// (hit_list.h).  rays, width, height and cam as QueryArgs (rt_batch.h query_ray).  No MODE: the list's capacity
-// (4 / 8 / 16 >= max_hits), stack 30 / 40 / 64 and the occupancy choose the build.
+// The ordered-hits kernel (rt_hits.hip, rt_trace_hits): one ray per lane through the rt_fast.h pieces (make_ray,
+// inner_step, pop), the first max_hits accepted distances kept in a register list (hit_list.h).  rays, width, height
+// and cam as QueryArgs (rt_batch.h query_ray).  The list's capacity (4 / 8 / 16 >= max_hits), stack 30 / 40 / 64 and
+// the occupancy choose the build.
 struct HitsArgs {
     const rt_ray* rays;  // null: camera mode
     rt_hit* hits;        // count * max_hits records
@@ -143,14 +150,7 @@ struct HitsArgs {
     GPUCamera cam;
     int max_hits;
     uint32_t flags;  // RT_HITS_*
-    const GeometrySphere* spheres;
-    int sphere_count;
-    int scene_fast;
-    const GPUFace* faces;
-    const GPUVertex* vertices;
-    const GPUBVHNode* nodes;  // the mirror's private node array
-    const FlatTri* tris;
-    const float4 *tree, *ltris;  // null: the scene has no leaf tree
+    WalkScene s;
 };
 hipError_t launch_hits(int stack, int waves_per_simd, const HitsArgs& a, hipStream_t s);
 

@@ -10,6 +10,9 @@ tests upload it.
   product(which)    bunny / bunny4 with 4096 points: a third uniform in the root box, a third on and near the surface
                     (first hits of camera rays from query_ref), a third 2 to 8 box diagonals away; half of all with a
                     finite radius
+  deck(name, spheres) scene_cases.py's decks (BVHs 29 / 39 / 62 levels deep: the stack-40 and stack-64 builds, and the
+                    deepest scene allowed), as they are or without their sphere, with 64 points: the deck's apex
+                    (0, 0, 0) with radius inf, the rest uniform in +-3; every fourth with radius 0.5
 """
 import functools
 
@@ -18,6 +21,7 @@ import numpy as np
 import adversarial_cases as AC
 import query_ref as Q
 import rt_testlib as T
+import scene_cases as SC
 
 F32 = np.float32
 INF = np.inf
@@ -173,6 +177,48 @@ def adversarial(name):
     order = np.random.default_rng(20251022).permutation(len(pts))
     return {"case": case, "scene": case.scene, "arrays": arrays_of(case.scene), "points": np.ascontiguousarray(pts[order]),
             "tree": case.tree}
+
+
+# --- the decks --------------------------------------------------------------------------------------------------------
+DECKS = {"deck29": 29, "deck39": 39, "deck62": 62}  # name -> depth
+
+
+@functools.lru_cache(maxsize=None)
+def deck_scene(name, spheres=True):
+    """The built deck.  Spheres are no part of the BVH: without its sphere the deck has the same nodes, and the kernel's
+    best is still inf when the walk starts (first_descent_pushes)."""
+    case = SC.BY_NAME[name]
+    if not spheres:
+        case = dict(case, prims=[p for p in case["prims"] if p[0] != "sphere"])
+    s = SC.apply_product(T.load_rt(), case)
+    s.build()
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def deck(name, spheres=True):
+    s = deck_scene(name, spheres)
+    pts = np.zeros((64, 4), dtype=F32)
+    pts[1:, 0:3] = np.random.default_rng(DECKS[name]).uniform(-3.0, 3.0, size=(63, 3))
+    pts[:, 3] = INF
+    pts[3::4, 3] = 0.5
+    return {"scene": s, "arrays": arrays_of(s), "points": pts}
+
+
+def first_descent_pushes(rt, A, p, best=INF):
+    """The entries rt_closest.hip's walk pushes on its way from the root to the first leaf it reaches, replayed on the
+    host node array with closest.h's bound (rt.closest_bound_host): the nearer child first, the other pushed when both
+    are within `best` (squared) -- which no leaf has lowered yet."""
+    node = pushes = 0
+    while A.count[node] == 0:
+        l = int(A.first[node])
+        bl, br = (rt.closest_bound_host(p, A.bmin[c], A.bmax[c]) for c in (l, l + 1))
+        tl, tr = not bl > best, not br > best
+        if not (tl or tr):
+            break
+        pushes += tl and tr
+        node = l if tl and (not tr or bl <= br) else l + 1
+    return pushes
 
 
 # --- the product scenes -----------------------------------------------------------------------------------------------

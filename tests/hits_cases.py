@@ -10,6 +10,8 @@ query_ref.Arrays) and left unchanged.
       box          a closed single-sided box (add_quad x 6) and rays from 512 points around it
       advA, advB   adversarial_cases.py's pinwheel scenes (coplanar triangles with twins: a big leaf / a leaf tree)
                    with every fourth ray of their ray sets
+      deck29, deck39, deck62   scene_cases.py's decks (BVHs 29 / 39 / 62 levels deep: the stack-40 and stack-64 builds, and
+                   the deepest scene allowed) with the 53x29 pixel-centre rays of their camera, at the deck's apex
   reference(name, k, flags)   hits_ref.trace of that set
   scene(name)             the built (not uploaded) Scene of a named set
 """
@@ -22,10 +24,12 @@ import closest_cases as CC
 import hits_ref as HR
 import query_ref as Q
 import rt_testlib as T
+import scene_cases as SC
 
 F32 = np.float32
 W, H = 64, 36
 W4, H4 = 32, 18
+DECKS = CC.DECKS  # name -> depth
 BOX_LO, BOX_HI = np.array([-1.0, -0.5, 2.0]), np.array([1.5, 1.0, 4.0])
 DIRECTIONS = ((0.36, 0.48, 0.8), (-0.6, 0.64, -0.48), (0.8, -0.36, 0.48))  # contains()'s
 
@@ -81,6 +85,8 @@ def scene(name):
         return box_scene()
     if name in ("advA", "advB"):
         return adversarial(name).scene
+    if name in DECKS:
+        return CC.deck_scene(name)
     raise KeyError(name)
 
 
@@ -130,6 +136,9 @@ def rays(name):
         case = adversarial(name)
         base, _ = AC.base_rays(case)
         return case.arrays(), np.ascontiguousarray(base[::4])
+    if name in DECKS:
+        s, w, h = scene(name), *SC.ROOM_SIZE
+        return CC.arrays_of(s), Q.camera_rays(np.frombuffer(bytes(s.camera()), dtype=F32), w, h)
     raise KeyError(name)
 
 
@@ -137,6 +146,13 @@ def rays(name):
 def reference(name, k, flags=0):
     A, r = rays(name)
     return HR.trace(A, r, k, flags)
+
+
+@functools.lru_cache(maxsize=None)
+def deck_pending(name):
+    """Per ray of a deck under COUNT_ALL (nothing is cut: the deepest walk), the most entries the kernel's stack holds."""
+    A, r = rays(name)
+    return HR.trace(A, r, 1, HR.COUNT_ALL, pending=True)[2]
 
 
 def same_rows(got, want, what, nan_payload_free=False):

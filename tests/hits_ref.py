@@ -5,7 +5,9 @@ for the slab test.  The one quantity the batches do not return, the sign of the 
 numpy float32 in rt_math.h's operation order (cross: a.y * b.z - b.y * a.z ...; dot: (x + y) + z).
 
 trace(arrays, rays, k, flags) returns (hits (N, k, 12) float32 rt_hit rows, counts (N,) int32: the list's length, or
-under COUNT_ALL the total)."""
+under COUNT_ALL the total).  With pending=True a third array follows: per ray, the most entries the kernel's stack
+holds at once (rt_fast.h inner_step: a left child goes onto it when its box is entered at all -- exit >= entry and
+exit > 0, whatever the bound -- and the right child is continued), read off this DFS whenever it enters a node."""
 import numpy as np
 
 import query_ref as Q
@@ -47,7 +49,7 @@ def det_sign(nd, v0, v1, v2):
     return ((e1[:, 0] * px).astype(F32) + (e1[:, 1] * py).astype(F32)).astype(F32) + (e1[:, 2] * pz).astype(F32)
 
 
-def trace(arrays, rays, k, flags=0):
+def trace(arrays, rays, k, flags=0, pending=False):
     A = arrays if isinstance(arrays, Q.Arrays) else Q.Arrays(arrays)
     L = Q._glm()
     rays = np.ascontiguousarray(rays, dtype=F32).reshape(-1, 8)
@@ -57,6 +59,7 @@ def trace(arrays, rays, k, flags=0):
     hits = np.zeros((n, k, 12), dtype=F32)
     hits_u = hits.view(np.uint32)
     counts = np.zeros(n, dtype=np.int32)
+    held_max = np.zeros(n, dtype=np.int32)
     ns = A.sph_c.shape[0]
     s_hit, s_dist = np.zeros(max(ns, 1), np.int32), np.zeros(max(ns, 1), F32)
     with np.errstate(all="ignore"):
@@ -71,16 +74,22 @@ def trace(arrays, rays, k, flags=0):
                 for i in range(ns):
                     if s_hit[i]:
                         lst.offer(s_dist[i], 1, i)
-            stack = [0]
-            while stack:
-                node = stack.pop()
+            def slab(node):
                 t1 = (A.bmin[node] - ro) / rd
                 t2 = (A.bmax[node] - ro) / rd
                 lo, hi = np.fmin(t1, t2), np.fmax(t1, t2)
-                tmin = np.fmax(np.fmax(lo[0], lo[1]), lo[2])
-                tmx = np.fmin(np.fmin(hi[0], hi[1]), hi[2])
+                return np.fmax(np.fmax(lo[0], lo[1]), lo[2]), np.fmin(np.fmin(hi[0], hi[1]), hi[2])
+
+            stack, held = [0], [False]  # held: whether the kernel's stack would hold that entry (pending only)
+            while stack:
+                node = stack.pop()
+                tmin, tmx = slab(node)
+                if pending:
+                    held.pop()
                 if not (tmx >= tmin and tmin < lst.bound() and tmx > 0):
                     continue
+                if pending:
+                    held_max[r] = max(held_max[r], sum(held))
                 c = int(A.count[node])
                 if c > 0:
                     ids, v0, v1, v2 = A.leaf(node)
@@ -99,6 +108,9 @@ def trace(arrays, rays, k, flags=0):
                 else:
                     stack.append(int(A.first[node]))
                     stack.append(int(A.first[node]) + 1)
+                    if pending:
+                        lmin, lmx = slab(int(A.first[node]))
+                        held += [bool(lmx >= lmin and lmx > 0), False]
             hits[r, :, 0] = tmax
             for j, (t, kind, pid, bx, by) in enumerate(lst.entries):
                 pos = ro + nd * t
@@ -117,4 +129,4 @@ def trace(arrays, rays, k, flags=0):
                 hits[r, j, 4:7], hits[r, j, 7] = nrm, bx
                 hits[r, j, 8:11], hits[r, j, 11] = pos, by
             counts[r] = lst.total if count_all else len(lst.entries)
-    return hits, counts
+    return (hits, counts, held_max) if pending else (hits, counts)

@@ -197,6 +197,34 @@ def test_product_cases_hit_and_miss(which):
     assert (kind != 0).sum() >= 64 and (kind == 0).sum() >= 64
 
 
+@pytest.mark.parametrize("name", list(CC.DECKS))
+def test_decks_need_their_deep_stacks(name):
+    """What tests/test_gpu_closest.py's deck cases lean on, on the host alone.  The BVH is as deep as the deck's name
+    says.  From the apex with best = inf both children of every node pass, so the first near-first descent pushes one
+    entry per level: exactly `depth`.  That is the kernel's state on the deck without its sphere.  With the sphere
+    (5.87 away, offered before the walk) the largest triangles' leaves are out of reach and the same descent pushes
+    16 / 21 / 33 entries: deck39 and deck62 still leave rtfast::Stack's 16 LDS entries, deck62 a stack of 30.  deck29
+    as built stays inside the LDS entries, so the sphere-less deck is the only case in which the stack-40 build reads
+    and writes its private overflow entries, and the only one that fills a stack to its depth: both must stay."""
+    rt = T.load_rt()
+    depth = CC.DECKS[name]
+    with_sphere, plain = CC.deck(name), CC.deck(name, spheres=False)
+    apex = with_sphere["points"][0]
+    assert apex.tolist() == [0, 0, 0, np.inf] and plain["points"].tobytes() == with_sphere["points"].tobytes()
+    assert with_sphere["scene"].max_depth() == plain["scene"].max_depth() == depth
+    A = plain["arrays"]
+    assert len(A.sph_c) == 0 and np.array_equal(plain["scene"].host_arrays()["nodes"], with_sphere["scene"].host_arrays()["nodes"])
+    assert CC.first_descent_pushes(rt, A, apex[0:3]) == depth
+    d2, _ = CR.sphere_candidates(apex[None, 0:3], with_sphere["arrays"].sph_c, with_sphere["arrays"].sph_r)
+    assert CC.first_descent_pushes(rt, A, apex[0:3], best=d2.min()) == {29: 16, 39: 21, 62: 33}[depth]
+    # the host brute force the GPU test compares against is the numpy restatement here too; hits, misses and radii occur
+    for c in (with_sphere, plain):
+        want = CR.closest(c["arrays"], c["points"])
+        CC.same_records(rt.closest_points_host(c["scene"], c["points"]), want, name)
+        kind = CR.fields(want)["kind"]
+        assert (kind == 2).sum() >= 16 and (kind == 0).sum() >= 4 and (c["points"][:, 3] == 0.5).sum() == 16
+
+
 def test_bunny_twins_tie_and_the_lower_index_wins():
     rt = T.load_rt()
     c = CC.product("bunny")

@@ -71,6 +71,21 @@ def test_product_scene(product, waves):
     CC.same_records(got.cpu().numpy(), want, f"{which}, waves {waves}")
 
 
+@pytest.mark.parametrize("spheres", [True, False], ids=["as built", "no sphere"])
+@pytest.mark.parametrize("name", list(CC.DECKS))
+def test_deep_stacks(name, spheres):
+    """BVHs 29, 39 and 62 levels deep: the stack-40 and stack-64 builds.  Without the deck's sphere the apex's walk
+    pushes one entry per level; as built, deck29's stays inside the stack's LDS entries, so only the sphere-less case
+    runs the stack-40 build's overflow entries (tests/test_closest_cpu.py test_decks_need_their_deep_stacks)."""
+    rt = T.load_rt()
+    c = CC.deck(name, spheres)
+    c["scene"].upload(0)
+    assert c["scene"].max_depth() == CC.DECKS[name]
+    want = rt.closest_points_host(c["scene"], c["points"])
+    got = rt.closest_points(c["scene"], dev(c["points"]))
+    CC.same_records(got.cpu().numpy(), want, f"{name}, spheres {spheres}")
+
+
 @pytest.mark.parametrize("count", [1, 63, 64, 65])
 def test_partial_waves(hand, count):
     rt = T.load_rt()

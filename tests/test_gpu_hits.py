@@ -99,6 +99,21 @@ def test_leaf_tree_scene(k):
         assert (counts == 4).sum() == 102
 
 
+@pytest.mark.parametrize("flags", [0, ALL])
+@pytest.mark.parametrize("k", [4, 16])
+@pytest.mark.parametrize("name", list(HC.DECKS))
+def test_deep_stacks(name, k, flags):
+    """BVHs 29, 39 and 62 levels deep: the stack-40 and stack-64 builds, their private overflow entries in use
+    (tests/test_hits_cpu.py test_decks_need_their_deep_stacks)."""
+    assert uploaded(name)[0].max_depth() == HC.DECKS[name]
+    check(name, k, flags)
+
+
+@pytest.mark.parametrize("waves", [5, 6, 7])
+def test_deep_stack_at_every_occupancy(waves):
+    check("deck39", 16, waves=waves)
+
+
 @pytest.mark.parametrize("name", ["advA", "advB"])
 def test_coplanar_twins(name):
     """The pinwheel's coplanar triangles and twins, as one big leaf (A) and as a leaf tree (B): equal distances, which the

@@ -156,6 +156,26 @@ def test_box_parity_is_containment():
         assert ((totals & 1) == inside).all(), d
 
 
+@pytest.mark.parametrize("name", list(HC.DECKS))
+def test_decks_need_their_deep_stacks(name):
+    """What tests/test_gpu_hits.py's deck cases lean on, on the reference alone: the BVH is as deep as the deck's name
+    says (29: the stack-40 build, 39 and 62: the stack-64 build), and under COUNT_ALL at least 16 rays hold more entries
+    at once than rtfast::Stack keeps in LDS (16) -- for deck39 and deck62 more than the next smaller build has at all
+    (30, 40).  The lists are full, short and empty in turn."""
+    depth = HC.DECKS[name]
+    assert HC.scene(name).max_depth() == depth
+    pending = HC.deck_pending(name)
+    print(name, "most entries held:", int(pending.max()), "; rays above 16 / 30 / 40:",
+          [int((pending > n).sum()) for n in (16, 30, 40)])
+    assert (pending > 16).sum() >= 16
+    assert depth != 39 or (pending > 30).sum() >= 16
+    assert depth != 62 or (pending > 40).sum() >= 16
+    _, c16 = HC.reference(name, 16)
+    _, totals = HC.reference(name, 16, HR.COUNT_ALL)
+    assert (c16 == 16).sum() == 49 and (c16 >= 8).sum() == 545 and (c16 == 0).sum() == 833
+    assert totals.max() == {29: 36, 39: 41, 62: 52}[depth]
+
+
 # --- the refusals that need no device ---------------------------------------------------------------------------------------
 D = 0x1000  # non-null, 16-byte aligned, never dereferenced on these paths
 DEFAULTS = dict(rays=D, hits=D, counts=D + 0x100000, count=64, max_hits=4)

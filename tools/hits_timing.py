@@ -47,13 +47,17 @@ def main():
     scene.set_viewport(W, H)
     scene.upload(0)
 
-    cam = torch.from_numpy(np.frombuffer(bytes(scene.camera()), dtype=np.float32).copy()).cuda()
-    i = torch.arange(W * H, device="cuda")
-    ux, uy = (((i % W).float() + 0.5) / float(W))[:, None], (((i // W).float() + 0.5) / float(H))[:, None]
-    camera = torch.zeros((W * H, 8), dtype=torch.float32, device="cuda")
-    camera[:, 0:3] = cam[0:3]
-    camera[:, 3] = rt.RAY_TMAX
-    camera[:, 4:7] = ((cam[12:15] + cam[6:9] * ux) + cam[9:12] * uy) - cam[0:3]
+    # the camera rays in the kernels' operation order (rt_batch.h query_ray), in numpy: IEEE float32 division, no
+    # contraction (a tensor divided by a scalar is multiplied by its reciprocal, which is an ulp off for some pixels)
+    F32 = np.float32
+    cam = np.frombuffer(bytes(scene.camera()), dtype=F32)
+    i = np.arange(W * H)
+    ux, uy = (((i % W).astype(F32) + F32(0.5)) / F32(W))[:, None], (((i // W).astype(F32) + F32(0.5)) / F32(H))[:, None]
+    rays = np.zeros((W * H, 8), dtype=F32)
+    rays[:, 0:3] = cam[0:3]
+    rays[:, 3] = rt.RAY_TMAX
+    rays[:, 4:7] = ((cam[12:15] + cam[6:9] * ux) + cam[9:12] * uy) - cam[0:3]
+    camera = torch.from_numpy(rays).cuda()
     first = rt.trace_rays(scene, camera)
     assert first.cpu().numpy().tobytes() == rt.trace_camera(scene, W, H).cpu().numpy().tobytes()
     f = rt.hit_fields(first)

@@ -4,10 +4,11 @@ command plus -Rpass-analysis=kernel-resource-usage into a temporary object (the 
 Needs no GPU.
 
     python tools/radiance_resources.py rt_radiance.hip > profiles/radiance_resources.txt
-    python tools/radiance_resources.py rt_hits.hip cap stack > profiles/hits_resources.txt
+    python tools/radiance_resources.py rt_hits.hip cap > profiles/hits_resources.txt
+    python tools/radiance_resources.py rt_closest.hip v > profiles/closest_resources.txt
 
-Two further arguments name the kernels' two template integers in their own order, where they are not <STACK, MODE>
-(rt_hits.hip: <CAP, STACK>, the list's capacity and the stack).
+A further argument labels the kernels' second template integer where it is not a MODE (the walk units' <STACK, V>:
+rt_hits.hip's list capacity, rt_closest.hip's unused 0).
 
 (tools/kernel_resources.py reads registers and spills from a built object's metadata; this one also has the
 compiler's LDS and occupancy figures and labels the rows by MODE and stack.)
@@ -54,13 +55,11 @@ def remarks(unit):
 
 def main():
     unit = sys.argv[1] if len(sys.argv) > 1 else "rt_radiance.hip"
-    named = len(sys.argv) > 3  # the template integers as the kernels declare them, else <STACK, MODE> shown as mode, stack
-    cols = (sys.argv[2], sys.argv[3]) if named else ("mode", "stack")
+    cols = (sys.argv[2] if len(sys.argv) > 2 else "mode", "stack")
     rows = []
     for name, f in remarks(unit):
         m = re.search(r"([a-z_]+_w\d)ILi(\d+)ELi(\d+)E", name)  # the mangled kernel<STACK, MODE>
-        first, second = (2, 3) if named else (3, 2)
-        label = (m.group(1), int(m.group(first)), int(m.group(second))) if m else (name, 0, 0)
+        label = (m.group(1), int(m.group(3)), int(m.group(2))) if m else (name, 0, 0)
         rows.append((label, f))
     rows.sort(key=lambda r: (r[0][1], r[0][2], r[0][0]))
     print(f"# {unit}: -Rpass-analysis=kernel-resource-usage with the build's flags (tools/radiance_resources.py); no GPU involved")
