@@ -6,6 +6,7 @@ by __graft_entry__.smoke() and by bench.py's cpu_baseline leg.
 import ctypes
 import importlib.util
 import os
+import re
 import sys
 
 import numpy as np
@@ -27,6 +28,21 @@ def load_rt():
     sys.modules["cuda_raytracing_amd"] = mod
     spec.loader.exec_module(mod)
     return mod
+
+
+def header_layout(text, name):
+    """(size, {field: offset}, [declared fields]) of a struct of include/rt_abi.h (`text`): the size and the offsets
+    its static_assert pins (None and {} where it has none), the field names in declaration order; an array counts as
+    one field."""
+    size = re.search(r"sizeof\(%s\) == (\d+)" % name, text)
+    offsets = dict((k, int(v)) for k, v in re.findall(r"offsetof\(%s, (\w+)\) == (\d+)" % name, text))
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    declared = []
+    for decl in body.split(";"):
+        decl = re.sub(r"\[\d+\]", "", decl.strip().replace("*", " "))
+        declared += re.findall(r"(\w+)\s*(?:,|$)", decl)
+    return (int(size.group(1)) if size else None), offsets, declared
 
 
 _P, _SZ, _I, _U32, _U64, _F = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float

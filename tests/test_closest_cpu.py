@@ -3,8 +3,6 @@ brute force (rt_closest_point_host) pinned bytewise to the numpy restatement of 
 the cull's bound on the host, and the conditions on the cases that keep the GPU comparisons of
 tests/test_gpu_closest.py from passing by being trivial."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -16,34 +14,6 @@ import rt_testlib as T
 
 F32 = np.float32
 DUMMY = 0x1000  # non-null, 16-byte aligned, never dereferenced on these paths
-
-
-def header_layout(text, name):
-    """(size, {field: offset} from the static_assert, [declared fields]) of a struct of rt_abi.h; arrays count as
-    one field."""
-    size = int(re.search(r"sizeof\(%s\) == (\d+)" % name, text).group(1))
-    offsets = dict((k, int(v)) for k, v in re.findall(r"offsetof\(%s, (\w+)\) == (\d+)" % name, text))
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    declared = []
-    for decl in body.split(";"):
-        decl = re.sub(r"\[\d+\]", "", decl.strip().replace("*", " "))
-        declared += re.findall(r"(\w+)\s*(?:,|$)", decl)
-    return size, offsets, declared
-
-
-@pytest.mark.parametrize("name, size", [("rt_point", 16), ("rt_nearest", 32), ("rt_closest_params", 32)])
-def test_struct_layout(name, size):
-    rt = T.load_rt()
-    cls = {"rt_point": rt.Point, "rt_nearest": rt.Nearest, "rt_closest_params": rt.ClosestParams}[name]
-    text = open(os.path.join(T.ROOT, "include", "rt_abi.h")).read()
-    hsize, offsets, declared = header_layout(text, name)
-    fields = [f for f, _ in cls._fields_]
-    assert hsize == size == ctypes.sizeof(cls)
-    assert declared == fields, (declared, fields)
-    assert set(offsets) == set(fields)  # the header pins every offset
-    for k, off in offsets.items():
-        assert getattr(cls, k).offset == off, k
 
 
 def test_symbols_and_binding():

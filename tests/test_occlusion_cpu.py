@@ -3,7 +3,6 @@ direction table, and the conditions on the CPU reference that keep the GPU compa
 tests/test_gpu_occlusion.py from passing by being trivial."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,29 +13,6 @@ import rt_testlib as T
 
 F32 = np.float32
 DUMMY = 0x1000  # non-null, 16-byte aligned, never dereferenced on these paths
-
-
-def header_layout(text, name):
-    size = int(re.search(r"sizeof\(%s\) == (\d+)" % name, text).group(1))
-    offsets = dict((k, int(v)) for k, v in re.findall(r"offsetof\(%s, (\w+)\) == (\d+)" % name, text))
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    declared = [n for decl in body.split(";") for n in re.findall(r"(\w+)\s*(?:,|$)", decl.strip().replace("*", " "))]
-    return size, offsets, declared
-
-
-@pytest.mark.parametrize("name, size", [("rt_occlusion_params", 32), ("rt_ao_params", 72)])
-def test_struct_layout(name, size):
-    rt = T.load_rt()
-    cls = {"rt_occlusion_params": rt.OcclusionParams, "rt_ao_params": rt.AoParams}[name]
-    text = open(os.path.join(T.ROOT, "include", "rt_abi.h")).read()
-    hsize, offsets, declared = header_layout(text, name)
-    fields = [f for f, _ in cls._fields_]
-    assert hsize == size == ctypes.sizeof(cls)
-    assert declared == fields, (declared, fields)
-    assert set(offsets) == set(fields)  # the header pins every offset
-    for k, off in offsets.items():
-        assert getattr(cls, k).offset == off, k
 
 
 def test_symbols_and_binding():

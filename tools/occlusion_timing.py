@@ -71,7 +71,7 @@ def main():
     assert torch.cuda.is_available(), "occlusion_timing needs a GPU"
     rt = G.load_package()
     if args.lib:
-        rt.LIB_PATH = os.path.abspath(args.lib)
+        rt._abi.LIB_PATH = os.path.abspath(args.lib)  # lib() reads it at its first call, in the module that loads the library
     scene_name, W, H, _, _, _ = bench.CONFIGS[args.config]
     torch.cuda.set_device(0)
     scene = rt.Scene()
